@@ -79,7 +79,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-gpu-dryrun", action="store_true",
                     help="launcher / sharding / reduction only (gloo, no GPU, nothing decoded): CPU test of the multi-rank path")
     ap.add_argument("--master-port", type=int, default=0)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (best paths, lattice sizes, a seeded "
+                         "sample of the scores and of the raw lattices; rank 0's shard) as DIR/<name>.npy, float32 / float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -407,6 +413,87 @@ def measured_traffic(args, world, kernel_ms, ref_order=True):
     except (OSError, KeyError, ValueError) as e:
         return None, "unreadable PMC record: %r" % (e,)
 
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_PART_BYTES = 16 << 20      # per part (best paths, score rows, raw lattices): the files stay under 64 MB in all
+# (state_final is +inf for a state that is not final: the dump keeps the final states' indices and costs instead)
+RAW_LATTICE_FIELDS = ("state_frame", "state_hclg", "arc_src", "arc_dst", "arc_il", "arc_ol", "arc_g", "arc_a")
+
+
+def _as_dump(a):
+    """float32 stays float32; integers become float64 (exact below 2^53)."""
+    a = np.asarray(a)
+    return a.astype(np.float32) if a.dtype == np.float32 else a.astype(np.float64)
+
+
+def dump_outputs(out_dir, dec, loglikes, off):
+    """What the timed step hands its caller, from its LAST step: per utterance the best path (GetBestPath: alignment, words,
+    graph and acoustic cost) and the raw lattice's size; a fixed, seeded sample of the raw lattices themselves (final weights
+    as the final states' indices and costs) and of the scaled log-likelihood rows the forward pass computed.  Same
+    arguments, same inputs: two builds compare file by file.  Every value written is finite (ValueError otherwise).
+    Returns (number of files, bytes)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n_utts, frames = len(off) - 1, int(off[-1])
+    out = {}
+    rng = np.random.default_rng(20151001)
+    # best paths of every utterance, or of a seeded sample of utterances when that would pass its part of the budget
+    bp = dec.get_best_paths()
+    per_utt = 8.0 * (len(bp["alignment"]) + len(bp["words"])) / max(n_utts, 1)
+    keep = n_utts if per_utt * n_utts <= DUMP_PART_BYTES else max(1, int(DUMP_PART_BYTES // per_utt))
+    utts = np.arange(n_utts) if keep >= n_utts else np.sort(rng.choice(n_utts, keep, replace=False))
+    ao, wo = bp["ali_off"], bp["words_off"]
+    out["best_path_utterances"] = utts
+    out["best_path_alignment"] = np.concatenate([bp["alignment"][ao[u]:ao[u + 1]] for u in utts] or [np.zeros(0, np.int32)])
+    out["best_path_alignment_offsets"] = np.concatenate([[0], np.cumsum(ao[utts + 1] - ao[utts])])
+    out["best_path_words"] = np.concatenate([bp["words"][wo[u]:wo[u + 1]] for u in utts] or [np.zeros(0, np.int32)])
+    out["best_path_words_offsets"] = np.concatenate([[0], np.cumsum(wo[utts + 1] - wo[utts])])
+    out["best_path_graph_cost"] = bp["graph_cost"][utts]
+    out["best_path_acoustic_cost"] = bp["acoustic_cost"][utts]
+    _, ls = dec.stats_batch(counters=False)
+    out["lattice_num_tokens"] = ls["num_tokens"]
+    out["lattice_num_links"] = ls["num_links"]
+    # scaled log-likelihoods: seeded rows
+    n_pdf = int(loglikes.shape[1])
+    rows = np.sort(rng.choice(frames, min(frames, max(1, DUMP_PART_BYTES // (4 * n_pdf))), replace=False))
+    out["loglikes_sample_rows"] = rows
+    out["loglikes_sample"] = loglikes[torch.from_numpy(rows).to(loglikes.device)].cpu().numpy()
+    # raw lattices (GetRawLattice, canonical form) of seeded utterances, as many as fit the part's budget
+    lat = {k: [] for k in RAW_LATTICE_FIELDS}
+    fin_state, fin_cost = [], []
+    lat_utts, st_off, arc_off, fin_off, used = [], [0], [0], [0], 0
+    for u in rng.permutation(n_utts)[:64]:
+        L = dec.get_raw_lattice(int(u))
+        size = 8 * (3 * len(L["state_frame"]) + 6 * len(L["arc_src"]))
+        if lat_utts and used + size > DUMP_PART_BYTES:
+            break
+        used += size
+        lat_utts.append(int(u))
+        for k in RAW_LATTICE_FIELDS:
+            lat[k].append(L[k])
+        fin = np.flatnonzero(np.isfinite(L["state_final"]))      # the final states (index within the utterance's lattice)
+        fin_state.append(fin)
+        fin_cost.append(L["state_final"][fin])
+        fin_off.append(fin_off[-1] + len(fin))
+        st_off.append(st_off[-1] + len(L["state_frame"]))
+        arc_off.append(arc_off[-1] + len(L["arc_src"]))
+    out["raw_lattice_utterances"] = np.asarray(lat_utts)
+    out["raw_lattice_state_offsets"] = np.asarray(st_off)
+    out["raw_lattice_arc_offsets"] = np.asarray(arc_off)
+    out["raw_lattice_final_offsets"] = np.asarray(fin_off)
+    out["raw_lattice_final_states"] = np.concatenate(fin_state) if fin_state else np.zeros(0)
+    out["raw_lattice_final_cost"] = np.concatenate(fin_cost) if fin_cost else np.zeros(0, np.float32)
+    for k in RAW_LATTICE_FIELDS:
+        out["raw_lattice_" + k] = np.concatenate(lat[k]) if lat[k] else np.zeros(0, np.float32)
+    out = {name: _as_dump(a) for name, a in out.items()}
+    bad = [name for name, a in out.items() if not np.isfinite(a).all()]
+    if bad:
+        raise ValueError("--dump-outputs: non-finite values in %s" % ", ".join(bad))
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, total
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(out), total
+
 
 def dryrun(args, rank, world):
     """CPU test of the multi-rank path: gloo process group, the strong-scaling partition,
@@ -539,7 +626,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(feats_h, off_h, steps, warmup, end_to_end=True):
+    def run(feats_h, off_h, steps, warmup, end_to_end=True, dump_dir=None):
         """Times `steps` steps over the shard (feats_h, off_h); returns the per-rank record."""
         n_utts = len(off_h) - 1
         frames = int(off_h[-1])
@@ -693,6 +780,7 @@ def main():
         join_background()
         sync()
         elapsed = time.perf_counter() - t0
+        dumped = dump_outputs(dump_dir, dec, loglikes, off_h) if dump_dir else None   # (after the timed region)
         pipelined = pipelined and not pipe["disabled"]   # (a failed background forward pass: the rest ran one after the other)
         main_stats = dict(stats)
         # ---- the same step strictly one after the other (round-to-round comparison with the unpipelined headline of
@@ -798,9 +886,9 @@ def main():
                     total_frames=float(tot[0].item()), tot_like=float(tot[1].item()),
                     n_ok=int(tot[2].item()), stats=dict(stats), kernel_ms=float(np.mean(kernel_ms)),
                     per_rank_kernel_ms=[float(x) for x in kms.tolist()], frames=frames, n_utts=n_utts,
-                    longest=int(np.diff(off_h).max()) if n_utts else 0)
+                    longest=int(np.diff(off_h).max()) if n_utts else 0, dumped=dumped)
 
-    weak = run(feats, off, args.steps, args.warmup)
+    weak = run(feats, off, args.steps, args.warmup, dump_dir=args.dump_outputs if rank == 0 else None)
     strong_rec = run(strong[0], strong[1], args.steps, args.warmup, end_to_end=False) if strong is not None else None
 
     if rank == 0:
@@ -863,6 +951,9 @@ def main():
             "per_rank_kernel_ms": weak["per_rank_kernel_ms"],
             "loglike_per_frame": st["tot_like"] / weak["frames"],
         }
+        if weak["dumped"] is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": weak["dumped"][0], "bytes": weak["dumped"][1],
+                                   "what": "the last timed step's outputs of rank 0's shard (bench.dump_outputs)"}
         ex = weak.get("extra") or {}
         if "unpipelined" in ex:
             u_ = ex["unpipelined"]

@@ -30,15 +30,22 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def ref_lib():
-    """The reference's own CPU code compiled from /root/reference (only where present)."""
+def _ref_live():
+    """The reference's own CPU code compiled from /root/reference (only where present), else None."""
     from oracle import binding
-    if not binding.have_ref():
-        if os.path.exists("/root/reference/src"):
-            binding.build(ref=True)
-        else:
-            pytest.skip("oracle/_ref not built and /root/reference absent")
-    return binding.OracleLib("ref")
+    if not binding.have_ref() and os.path.exists("/root/reference/src"):
+        binding.build(ref=True)
+    return binding.OracleLib("ref") if binding.have_ref() else None
+
+
+@pytest.fixture
+def ref_lib(request, _ref_live):
+    """The reference's answers for this test: the compiled reference where it is built, elsewhere the answers it
+    gave to the same inputs (tests/golden/reference_calls, tests/refrecord.py)."""
+    import refrecord
+    ref = refrecord.Reference(request.node.nodeid, _ref_live, record=bool(os.environ.get("KH_RECORD_REFERENCE")))
+    yield ref
+    ref.save()
 
 
 @pytest.fixture(scope="session")

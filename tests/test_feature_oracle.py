@@ -71,9 +71,8 @@ def test_golden_deltas_and_cmvn():
         assert np.array_equal(y.view(np.int32), g[key].view(np.int32))  # MulColsVec + AddVecToRows: bit-exact
 
 
-@pytest.mark.skipif(not B.have_ref(), reason="oracle/_ref is only built where /root/reference exists")
-def test_against_compiled_reference_on_fresh_input():
-    ko, ref = B.OracleLib("ko"), B.OracleLib("ref")
+def test_against_compiled_reference_on_fresh_input(ref_lib):
+    ko, ref = B.OracleLib("ko"), ref_lib
     w = wave(99, 16000 + 55)
     for name, cfg in MFCC_CONFIGS.items():
         check_mfcc(ko.mfcc_compute(w, **cfg), ref.mfcc_compute(w, **cfg))

@@ -1,6 +1,6 @@
 """CPU: pins the numpy specification of OnlineIvectorFeature (oracle/ivector_oracle.py) piece by
-piece to the REFERENCE compiled into oracle/_ref (only where /root/reference is present; the
-committed fixture tests/golden/ivector.npz holds the same reference outputs for the GPU box):
+piece to the REFERENCE compiled into oracle/_ref (live where it is built, elsewhere its recorded answers to the
+same inputs: tests/refrecord.py; the committed fixture tests/golden/ivector.npz holds reference outputs too):
   * online CMVN -> splice -> LDA through the reference's OnlineCmvn / OnlineSpliceFrames /
     OnlineTransform (feat/online-feature.cc), window shorter and longer than the utterance;
   * UBM log-likelihoods through DiagGmm::LogLikelihoods;
@@ -28,7 +28,7 @@ def small_model(rng, **kw):
     return workloads.make_ivector_extractor(rng, **args)
 
 
-def ref_chain(m, X):
+def _live_chain(m, X):
     lib = C.CDLL(B.REF_SO)
     T, D = X.shape
     lda = np.ascontiguousarray(m["lda_mat"], np.float32)
@@ -44,7 +44,7 @@ def ref_chain(m, X):
     return o1, o2, o3
 
 
-def ref_cgd(A, b, x0, iters):
+def _live_cgd(A, b, x0, iters):
     lib = C.CDLL(B.REF_SO)
     S = len(b)
     r, c = np.tril_indices(S)
@@ -55,7 +55,7 @@ def ref_cgd(A, b, x0, iters):
     return x, k
 
 
-def ref_cmvn_speaker(m, X, speaker_stats):
+def _live_cmvn_speaker(m, X, speaker_stats):
     lib = C.CDLL(B.REF_SO)
     T, D = X.shape
     gs = np.ascontiguousarray(m["global_cmvn_stats"], np.float64)
@@ -69,6 +69,18 @@ def ref_cmvn_speaker(m, X, speaker_stats):
     return out, st
 
 
+def ref_chain(ref, m, X):
+    return ref.call("online_cmvn_splice_lda", _live_chain, m, X)
+
+
+def ref_cgd(ref, A, b, x0, iters):
+    return ref.call("linear_cgd", _live_cgd, A, b, x0, iters)
+
+
+def ref_cmvn_speaker(ref, m, X, speaker_stats):
+    return ref.call("online_cmvn_speaker", _live_cmvn_speaker, m, X, speaker_stats)
+
+
 def cases():
     rng = np.random.default_rng(12)
     m = small_model(rng)
@@ -77,11 +89,10 @@ def cases():
     return m, m2, X
 
 
-@pytest.mark.skipif(not B.have_ref(), reason="oracle/_ref not built")
-def test_feature_chain_and_solver_match_the_reference():
+def test_feature_chain_and_solver_match_the_reference(ref_lib):
     m, m2, X = cases()
     for mm in (m, m2):
-        lda, lda_n, cm = ref_chain(mm, X)
+        lda, lda_n, cm = ref_chain(ref_lib, mm, X)
         np.testing.assert_allclose(IO.online_cmvn(X, mm), cm, rtol=0, atol=2e-6)
         np.testing.assert_allclose(IO.splice_lda(X, mm), lda, rtol=0, atol=2e-6)
         np.testing.assert_allclose(IO.splice_lda(IO.online_cmvn(X, mm), mm), lda_n, rtol=0, atol=5e-6)
@@ -93,15 +104,14 @@ def test_feature_chain_and_solver_match_the_reference():
         x0 = np.zeros(S)
         x0[0] = 2.0
         for iters in (3, 15):
-            want, k = ref_cgd(A, b, x0, iters)
+            want, k = ref_cgd(ref_lib, A, b, x0, iters)
             got, k2 = IO.linear_cgd(A, b, x0.copy(), iters)
             assert k == k2
             np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-12)
     # UBM log-likelihoods: the reference's DiagGmm on the normalised features
     g, mi, iv = IO.ubm_params(m)
     Fn = IO.splice_lda(IO.online_cmvn(X, m), m)
-    ref = B.OracleLib("ref")
-    want = ref.ref_diag_gmm_loglikes(m["ubm_weights"], m["ubm_means"], m["ubm_vars"], Fn)
+    want = ref_lib.ref_diag_gmm_loglikes(m["ubm_weights"], m["ubm_means"], m["ubm_vars"], Fn)
     got = g[None, :] + Fn @ mi.T - 0.5 * ((Fn * Fn) @ iv.T)
     np.testing.assert_allclose(got, want, rtol=0, atol=2e-4)
 
@@ -157,15 +167,14 @@ def test_golden_fixture_matches_the_specification():
     np.testing.assert_allclose(got, z["cg_x"], rtol=1e-10, atol=1e-12)
 
 
-@pytest.mark.skipif(not B.have_ref(), reason="oracle/_ref not built")
-def test_cmvn_with_speaker_state_matches_the_reference():
+def test_cmvn_with_speaker_state_matches_the_reference(ref_lib):
     """The adaptation state's CMVN half: OnlineCmvn started from the speaker stats of the previous
     utterances (SetState) and the stats GetState returns, chained over three utterances of a speaker."""
     m, m2, X = cases()
     for mm in (m, dict(m2, speaker_frames=20)):
         sp_ref = sp_ora = None
         for seg in (X[:40], X[40:52], X[52:]):
-            want, st_ref = ref_cmvn_speaker(mm, seg, sp_ref)
+            want, st_ref = ref_cmvn_speaker(ref_lib, mm, seg, sp_ref)
             got, st_ora = IO.online_cmvn(seg, mm, sp_ora, True)
             np.testing.assert_allclose(got, want, rtol=0, atol=2e-6)
             np.testing.assert_allclose(st_ora, st_ref, rtol=1e-12, atol=1e-9)
@@ -240,8 +249,7 @@ def test_online_ivector_feature_object_and_silence_weighting_host_logic():
     assert not o2.OnlineSilenceWeighting(t2p, "", 0.0).active() and not o2.OnlineSilenceWeighting(t2p, "1:2", 1.0).active()
 
 
-@pytest.mark.skipif(not B.have_ref(), reason="oracle/_ref not built")
-def test_exact_solve_fallback_of_linear_cgd_matches_the_reference():
+def test_exact_solve_fallback_of_linear_cgd_matches_the_reference(ref_lib):
     """LinearCgd falls back to SolveQuadraticProblem when the squared residual got worse (matrix/optimization.cc:546-563,
     sp-matrix.cc:659-734: eigenvalues floored at l_max / 1e4, the step taken only if the auxiliary function does not decrease).
     Ill-conditioned systems cut off after one or two iterations trigger it; the restatement against the compiled reference."""
@@ -266,7 +274,7 @@ def test_exact_solve_fallback_of_linear_cgd_matches_the_reference():
                     else:
                         b = rng.standard_normal(S) * cond ** 0.5
                     got, k = IO.linear_cgd(A, b, x0.copy(), iters)
-                    want, k2 = ref_cgd(A, b, x0, iters)
+                    want, k2 = ref_cgd(ref_lib, A, b, x0, iters)
                     assert k == k2
                     # (eigenvectors of the small eigenvalues are only determined to ~1e-16 * cond by either eigen-solver)
                     tol = max(1e-9, 1e-13 * cond)

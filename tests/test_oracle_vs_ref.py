@@ -1,6 +1,6 @@
 """CPU, build container only: the restatement against the reference's own compiled
 CPU code (oracle/_ref) on fresh random shapes, beyond the committed fixtures.
-Skipped where /root/reference (hence oracle/_ref) is absent."""
+Where oracle/_ref is not built, the answers it gave to the same inputs (tests/golden/reference_calls)."""
 import importlib
 
 import numpy as np

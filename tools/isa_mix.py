@@ -7,7 +7,8 @@ Compiles the file for gfx950 with the library's flags (`hipcc -S`, device side o
 v_readlane / v_writelane (scalar registers spilled into VGPR lanes: every reload is a VALU issue slot plus wait states -
 round 4 found a quarter of DecodeKernel's instructions there), scratch loads / stores and bytes (VGPR spills: a reload
 inside a loop waits on vmcnt(0), i.e. on the loop's own stores), ds_bpermute (cross-lane traffic on the LDS pipe) and DPP
-instructions.  The listing itself stays in /tmp/<file>.s for a look at the loops (grep for the kernel's mangled name).
+instructions.  The listing itself stays in old-kaldi-git_amd/build/<file>.s for a look at the loops (grep for the kernel's
+mangled name).
 What to watch when changing the decoder: scratch bytes of DecodeKernel<1,0> (132 at the end of round 4) - every build that
 raised it by 8-24 bytes lost 4-12 % on the GPU."""
 import collections
@@ -26,7 +27,9 @@ def main():
     src = next((a for a in args if not a.startswith("-")), "kh_decoder.hip")
     defs = [a for a in args if a.startswith("-")]
     path = src if os.path.exists(src) else os.path.join(ROOT, "old-kaldi-git_amd", "csrc", src)
-    out = os.path.join("/tmp", os.path.basename(path) + ".s")
+    objdir = os.path.join(ROOT, "old-kaldi-git_amd", "build")
+    os.makedirs(objdir, exist_ok=True)
+    out = os.path.join(objdir, os.path.basename(path) + ".s")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     subprocess.run([hipcc] + FLAGS + defs + [path, "-o", out], check=True, stderr=subprocess.DEVNULL)
     kernels, cur = {}, None

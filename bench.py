@@ -35,6 +35,14 @@ all-reduce of {frames, utterances, tot_like} (nnet-latgen-faster.cc:100-101,
 ONE 2620-utterance set sharded by sharding.partition_utterances, as the recipes
 split one data set over $nj jobs (steps/nnet2/decode.sh:130-136).
 
+A plain run does only what the headline needs: it builds the workload, warms up, times the K steps, writes
+--dump-outputs and prints the line (value, ms_per_step, rtf, search statistics, the roofline of the timed steps).
+--full adds every other leg: the CPU baselines, the unpipelined and canonical-rule repeats (value_unpipelined,
+value_canonical), the loops with determinization and with the front end (value_end_to_end, value_wave_to_lattice),
+the secondary legs of configs 2, 3, 5 and serving, and at N > 1 strong_scaling.  Every leg of --full runs after the
+timed steps (the CPU baselines' child is forked before the GPU is touched, but waits), so the headline is the same
+either way.
+
 RTF = elapsed * 100 / frames (nnet-latgen-faster.cc:179-182).
 """
 import argparse
@@ -65,6 +73,10 @@ def parse_args(argv=None):
     ap.add_argument("--utts", type=int, default=2620, help="utterances per GPU (test-clean has 2620)")
     ap.add_argument("--graph-states", type=int, default=10_000_000)
     ap.add_argument("--small", action="store_true", help="tiny model/graph for a quick functional run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline does not need: the CPU baselines, the unpipelined and canonical-rule "
+                         "repeats, the end-to-end and waveform loops, the secondary legs and, at N > 1, the strong-scaling leg "
+                         "(the --no-* options below drop single legs of a --full run)")
     ap.add_argument("--cpu-utts", type=int, default=20, help="utterances of the single-thread CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling leg at N > 1")
@@ -85,6 +97,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:       # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing else
+        args.no_cpu_baseline = args.no_strong = args.no_secondary = args.no_extra_legs = args.no_end_to_end = True
     return args
 
 
@@ -928,7 +942,7 @@ def main():
                                "i + 1's forward pass (kh_decoder_set_after_launch) while the host finishes step i (lattices, best "
                                "paths) - K forward passes and K decodes inside the timed region; steps_pipelined = false "
                                "(KH_BENCH_NO_PIPELINE=1, or a background pass failed on some rank): strictly one after the other; "
-                               "value_unpipelined is that figure in every run.  search = reference-order: LatticeFasterDecoder's own "
+                               "value_unpipelined (--full) is that figure.  search = reference-order: LatticeFasterDecoder's own "
                                "iteration order (HashList order, running next_cutoff; bit-exact against oracle mode 0), the library's "
                                "default; value_canonical / roofline.canonical_* = the opt-in order-independent rule E (oracle mode 3)"},
             "search_stats": {"arcs_expanded_per_frame": st["arcs"] / weak["frames"], "tokens_per_frame": st["toks"] / weak["frames"],

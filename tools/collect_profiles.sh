@@ -8,10 +8,10 @@ out=${1:-gpurun_out/profiles}; tag=${2:-r01}
 mkdir -p "$out"
 export TMPDIR=/tmp
 T=${PROFILE_TIMEOUT:-420}
-timeout -k 10 $T rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-extra-legs > "$out/${tag}_bench_under_rocprof.json" 2> "$out/kt.log"
+timeout -k 10 $T rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-extra-legs > "$out/${tag}_bench_under_rocprof.json" 2> "$out/kt.log"
 f=$(find "$out/kt" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/${tag}_bench_kernel_stats.csv"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 $T rocprofv3 --pmc $c --output-format csv -d "$out/pmc_$c" -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-extra-legs > "$out/pmc_$c.json" 2> "$out/pmc_$c.log"
+  timeout -k 10 $T rocprofv3 --pmc $c --output-format csv -d "$out/pmc_$c" -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-extra-legs > "$out/pmc_$c.json" 2> "$out/pmc_$c.log"
   f=$(find "$out/pmc_$c" -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python3 tools/pmc_summarize.py "$f" DecodeKernel > "$out/${tag}_pmc_$c.txt"
 done
@@ -20,7 +20,7 @@ done
   echo "# DecodeKernel, one launch: read request sizes and DRAM-side tallies in 32-byte units (separate rocprofv3 --pmc passes)"
   for set in "TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_32B_sum" "TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_DRAM_32B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" "TCC_EA0_WRREQ_WRITE_DRAM_sum TCC_EA0_WRREQ_WRITE_DRAM_32B_sum"; do
     rm -rf "$out/pmc_x"
-    timeout -k 10 $T rocprofv3 --pmc $set --output-format csv -d "$out/pmc_x" -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-extra-legs --no-strong > /dev/null 2> "$out/pmc_x.log"
+    timeout -k 10 $T rocprofv3 --pmc $set --output-format csv -d "$out/pmc_x" -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-extra-legs --no-strong > /dev/null 2> "$out/pmc_x.log"
     f=$(find "$out/pmc_x" -name "*counter_collection.csv" | head -1)
     [ -n "$f" ] && python3 tools/pmc_summarize.py "$f" DecodeKernel
   done
@@ -58,7 +58,7 @@ python3 tools/phases_extract.py "$out/canon.err" > "$out/${tag}_decoder_phases_c
 python3 tools/pmc_record.py "$out/${tag}_pmc_FETCH_SIZE.txt" "$out/${tag}_pmc_WRITE_SIZE.txt" "$out/${tag}_bench_kernel_stats.csv" "$out/${tag}_pmc_traffic.json" reference-order || { echo "collect_profiles: PMC record incomplete" >&2; exit 1; }
 cp "$out/${tag}_pmc_FETCH_SIZE.txt" "$out/${tag}_pmc_WRITE_SIZE.txt" "$out/${tag}_pmc_traffic.json" profiles/ || exit 1
 # (every leg of the line, the CPU baselines included: 5-8 minutes depending on the box - its own, longer limit)
-KH_DECODER_PROFILE=1 BENCH_VERBOSE=1 timeout ${PROFILE_BENCH_TIMEOUT:-1200} python3 bench.py --steps 3 --warmup 1 > "$out/${tag}_bench.json" 2> "$out/bench.err"
+KH_DECODER_PROFILE=1 BENCH_VERBOSE=1 timeout ${PROFILE_BENCH_TIMEOUT:-1200} python3 bench.py --full --steps 3 --warmup 1 > "$out/${tag}_bench.json" 2> "$out/bench.err"
 [ -s "$out/${tag}_bench.json" ] || { echo "collect_profiles: the bench line is empty (timeout?)" >&2; exit 1; }
 python3 tools/phases_extract.py "$out/bench.err" > "$out/${tag}_decoder_phases.txt"
 rm -rf "$out/kt" "$out"/pmc_FETCH_SIZE "$out"/pmc_WRITE_SIZE

@@ -18,7 +18,7 @@ pass() {  # name, program..., -- counters
   fi
   rm -rf "$out/$name"
 }
-B="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary"
 G="python3 tools/bench_gmm.py"
 pass mfma_bench $B -- SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY
 pass lds_bench $B -- SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS

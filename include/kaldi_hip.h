@@ -688,6 +688,39 @@ int kh_lattice_alphas_betas(int n_lats, const int32_t *lat_state_offsets,
                             const float *arc_acoustic, const float *state_final,
                             int viterbi, double *alpha, double *beta, double *tot);
 
+/* CompactLatticeShortestPath (lat/lattice-functions.cc:1043-1126) for a batch of top-sorted CompactLattices and n_points
+ * "score points" in one call (csrc/kh_latbest.hip).  HOST CSR as kh_lattice_forward_backward (arc_label = the word of a
+ * CompactLattice arc; final_graph / final_acoustic = the two values of the final weight, +inf / +inf = Zero; the strings
+ * stay with the caller).  A score point is what lattice-scale and lattice-add-penalty do to a weight before
+ * lattice-best-path searches: scales[4 p ...] = { lm_scale, acoustic2lm_scale, lm2acoustic_scale, acoustic_scale }
+ * (latbin/lattice-scale.cc:76-82, doubles) and penalties[p] (float).  Per lattice and point, in the reference's order:
+ *   (g, a) -> g' = (float)(s00 g + s01 a), a' = (float)(s10 g + s11 a), sums and products in double, Zero stays Zero
+ *   (fstext/lattice-weight.h:233-241); g' = g' + penalty in float on arcs with a label != 0, never on final weights
+ *   (lattice-functions.cc:1140-1143); cost = (double)g' + (double)a' (lattice-weight.h:799-801); the search of :1060-1086
+ *   (a predecessor is replaced only by a strictly smaller cost: on a tie the lowest-numbered source state stays); between
+ *   two consecutive path states the arc of smallest COST, the first on a tie (:1102-1121).
+ * Outputs (HOST), entry l * n_points + p: path_len = arcs on the path, -1 = no path (:1091; the caller counts a failure);
+ * the path's arcs as arc numbers relative to the lattice's first arc at path_arcs[path_offsets[l * n_points + p] ...]
+ * (path_offsets: n_lats * n_points + 1 entries, the caller's room per path; n_states - 1 always suffices, KH_EINVAL if a
+ * path does not fit); path_final_state = the state whose final weight ends the path; tot_graph / tot_acoustic = the float
+ * sums GetLinearSymbolSequence forms (lattice-best-path.cc:98): from 0, every path arc's g' / a' in path order, the final
+ * weight's last.  KH_EINVAL if a lattice is not top-sorted (an arc to a state that is not higher-numbered).
+ * The workspace is (n_states x 12 + longest path x 4) bytes x n_points per lattice in flight; lattices are taken longest
+ * first, as many per launch as half of the free device memory admits, or as
+ * kh_compact_lattice_best_paths_set_workspace_limit(bytes) admits: a setting of the CALLING THREAD (0 = back to
+ * automatic; one lattice always runs).  kh_compact_lattice_best_paths_last_timings: milliseconds the last call of this
+ * thread spent in { host preparation (validation, incoming-arc lists), upload, kernels, download (HIP events; the host's
+ * scatter and the allocations are not in these four), the whole call by the host's clock }, and its number of launches
+ * (may be NULL). */
+int kh_compact_lattice_best_paths(int n_lats, const int32_t *lat_state_offsets, const int64_t *arc_offsets,
+                                  const int32_t *arc_label, const int32_t *arc_nextstate, const float *arc_graph,
+                                  const float *arc_acoustic, const float *final_graph, const float *final_acoustic,
+                                  int n_points, const double *scales, const float *penalties, int32_t *path_len,
+                                  int32_t *path_arcs, const int64_t *path_offsets, int32_t *path_final_state,
+                                  float *tot_graph, float *tot_acoustic);
+int kh_compact_lattice_best_paths_set_workspace_limit(size_t bytes);
+int kh_compact_lattice_best_paths_last_timings(float *ms5, int32_t *n_launches);
+
 /* LatticeForwardBackwardMpeVariants (lat/lattice-functions.cc:740-919): criterion
  * "smbr" (is_mpfe = 0) or "mpfe".  tid2phone / tid2pdf = TransitionIdToPhone /
  * TransitionIdToPdf as arrays of num_tids + 1 entries indexed by transition-id;

@@ -1276,6 +1276,183 @@ def lattice_last_timings():
     return dict(upload_ms=ms[0], prep_ms=ms[1], sweeps_ms=ms[2], download_ms=ms[3])
 
 
+# ---------------------------------------------------------------- best paths over score points (csrc/kh_latbest.hip)
+def score_point(lm_scale=1.0, acoustic_scale=1.0, inv_acoustic_scale=1.0, acoustic2lm_scale=0.0, lm2acoustic_scale=0.0,
+                word_ins_penalty=0.0):
+    """What `lattice-scale [options] | lattice-add-penalty --word-ins-penalty=...` do to a weight, as the pair
+    (scale [4 doubles: lm, acoustic2lm, lm2acoustic, acoustic], penalty [float32]) compact_lattice_best_paths takes.  The
+    options are BaseFloat = float; with inv_acoustic_scale != 1 the acoustic scale is the FLOAT quotient 1.0 / inv
+    (latbin/lattice-scale.cc:72-82)."""
+    ac, inv = np.float32(acoustic_scale), np.float32(inv_acoustic_scale)
+    if not (ac == np.float32(1.0) or inv == np.float32(1.0)):       # KALDI_ASSERT :72
+        raise KhError("score_point: acoustic_scale == 1.0 || inv_acoustic_scale == 1.0")
+    if inv != np.float32(1.0):
+        ac = np.float32(1.0) / inv
+    scale = np.array([np.float32(lm_scale), np.float32(acoustic2lm_scale), np.float32(lm2acoustic_scale), ac], np.float64)
+    return scale, np.float32(word_ins_penalty)
+
+
+def compact_lattice_top_order(clat):
+    """The state numbering CompactLatticeShortestPath searches in (lat/lattice-functions.cc:1046-1052): None when the
+    lattice has the kTopSorted property (start state 0 and every arc to a higher-numbered state), else order[old] = new of
+    fst::TopSort (fst/topsort.h): reverse finishing order of a depth-first search from the start state, then from every
+    still unvisited state in number order, a state's arcs in order.  The numbering decides ties, so any other
+    topological order will not do.  Raises on a cycle (:1048-1049)."""
+    n = int(clat["n_states"])
+    start = int(clat.get("start", 0))
+    src, dst = np.asarray(clat["arc_src"], np.int64), np.asarray(clat["arc_dst"], np.int64)
+    if n == 0 or start < 0:         # no start state (:1055: the best path is empty); nothing to number
+        return None
+    if start >= n:
+        raise KhError("compact lattice: start state %d of %d states" % (start, n))
+    if start == 0 and bool(np.all(dst > src)):
+        return None
+    by_src = np.argsort(src, kind="stable")
+    off = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]).astype(np.int64)
+    nxt = dst[by_src].tolist()
+    off = off.tolist()
+    color = [0] * n          # white / grey / black
+    finish = []
+    for root in [start] + list(range(n)):
+        if color[root]:
+            continue
+        color[root] = 1
+        stack = [(root, off[root])]
+        while stack:
+            s, k = stack[-1]
+            if k < off[s + 1]:
+                stack[-1] = (s, k + 1)
+                t = nxt[k]
+                if color[t] == 0:
+                    color[t] = 1
+                    stack.append((t, off[t]))
+                elif color[t] == 1:
+                    raise KhError("Was not able to topologically sort lattice (cycles found?)")
+            else:
+                color[s] = 2
+                finish.append(s)
+                stack.pop()
+    order = np.empty(n, np.int64)
+    order[np.asarray(finish[::-1], np.int64)] = np.arange(n)
+    return order
+
+
+def compact_lattice_to_csr(clat):
+    """CompactLattice dict (kaldi_io.read_compact_lattice / determinize_lattice_pruned) -> the top-sorted CSR arrays of
+    kh_compact_lattice_best_paths, renumbered by compact_lattice_top_order when needed.  perm[j] = the dict's arc behind
+    CSR arc j, state_of[s] = the dict's state behind CSR state s."""
+    n = int(clat["n_states"])
+    src, dst = np.asarray(clat["arc_src"], np.int64), np.asarray(clat["arc_dst"], np.int64)
+    order = compact_lattice_top_order(clat)
+    state_of = np.arange(n, dtype=np.int64)
+    if order is not None:
+        src, dst = order[src], order[dst]
+        state_of = np.argsort(order)
+    perm = np.argsort(src, kind="stable")
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(np.bincount(src, minlength=n))
+    return dict(n_states=n, arc_offsets=off, arc_label=np.asarray(clat["arc_label"], np.int32)[perm],
+                arc_nextstate=dst[perm].astype(np.int32), arc_graph=np.asarray(clat["arc_g"], np.float32)[perm],
+                arc_acoustic=np.asarray(clat["arc_a"], np.float32)[perm],
+                final_graph=np.asarray(clat["final_g"], np.float32)[state_of],
+                final_acoustic=np.asarray(clat["final_a"], np.float32)[state_of], perm=perm, state_of=state_of)
+
+
+def compact_lattice_best_paths_raw(csrs, points, workspace_limit=None):
+    """kh_compact_lattice_best_paths on CSR dicts (compact_lattice_to_csr's layout, top-sorted).  points: a list of
+    (scale, penalty) as score_point returns.  Returns (path_len [n_lats x n_points], paths [list of lists of int32 arrays:
+    CSR arc numbers within the lattice], final_state, tot_graph, tot_acoustic [n_lats x n_points]).  workspace_limit
+    (bytes): bound the lattices in flight for this call (None = from the free device memory; the library keeps the limit
+    per thread, and it is set back before this returns)."""
+    n, K = len(csrs), len(points)
+    if n == 0 or K == 0:
+        raise KhError("compact_lattice_best_paths: no lattices or no score points")
+    soff = np.zeros(n + 1, np.int32)
+    for i, L in enumerate(csrs):
+        soff[i + 1] = soff[i] + L["n_states"]
+    aoff = [np.zeros(1, np.int64)]
+    base = 0
+    for L in csrs:
+        o = np.asarray(L["arc_offsets"], np.int64)
+        aoff.append(o[1:] + base)
+        base += int(o[-1])
+    aoff = np.ascontiguousarray(np.concatenate(aoff))
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt) for L in csrs]))
+    lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
+    g, a = cat("arc_graph", np.float32), cat("arc_acoustic", np.float32)
+    fg, fa = cat("final_graph", np.float32), cat("final_acoustic", np.float32)
+    scales = np.ascontiguousarray(np.stack([np.asarray(s, np.float64).reshape(4) for s, _ in points]))
+    pens = np.ascontiguousarray(np.asarray([p for _, p in points], np.float32))
+    room = np.repeat(np.maximum(np.diff(soff).astype(np.int64) - 1, 1), K)      # a path has at most n_states - 1 arcs
+    poff = np.zeros(n * K + 1, np.int64)
+    poff[1:] = np.cumsum(room)
+    plen, pfin = np.empty(n * K, np.int32), np.empty(n * K, np.int32)
+    parcs = np.empty(int(poff[-1]), np.int32)
+    tg, ta = np.empty(n * K, np.float32), np.empty(n * K, np.float32)
+    ip, fp = capi.c_int32_p, capi.c_float_p
+    if workspace_limit is not None:
+        check(lib().kh_compact_lattice_best_paths_set_workspace_limit(int(workspace_limit)))
+    try:
+        check(lib().kh_compact_lattice_best_paths(
+            n, soff.ctypes.data_as(ip), aoff.ctypes.data_as(capi.c_int64_p), lab.ctypes.data_as(ip), ns.ctypes.data_as(ip),
+            g.ctypes.data_as(fp), a.ctypes.data_as(fp), fg.ctypes.data_as(fp), fa.ctypes.data_as(fp), K,
+            scales.ctypes.data_as(capi.c_double_p), pens.ctypes.data_as(fp), plen.ctypes.data_as(ip), parcs.ctypes.data_as(ip),
+            poff.ctypes.data_as(capi.c_int64_p), pfin.ctypes.data_as(ip), tg.ctypes.data_as(fp), ta.ctypes.data_as(fp)))
+    finally:
+        if workspace_limit is not None:
+            check(lib().kh_compact_lattice_best_paths_set_workspace_limit(0))
+    paths = [[parcs[poff[i * K + p]:poff[i * K + p] + max(int(plen[i * K + p]), 0)].copy() for p in range(K)] for i in range(n)]
+    return plen.reshape(n, K), paths, pfin.reshape(n, K), tg.reshape(n, K), ta.reshape(n, K)
+
+
+def compact_lattice_best_paths(clats, points, workspace_limit=None):
+    """lattice-scale | lattice-add-penalty | lattice-best-path (CompactLatticeShortestPath, lat/lattice-functions.cc:1043-1126)
+    for a batch of CompactLattices (dict layout of kaldi_io.read_compact_lattice / determinize_lattice_pruned) and a list of
+    score points (score_point) in ONE device call.  Returns per lattice a list over the points of None (no path: the
+    reference's "Best-path failed") or dict(words = the non-zero labels of the path's arcs, alignment = the arcs'
+    transition-ids followed by the final state's (ConvertLattice + GetLinearSymbolSequence, lattice-best-path.cc:89-98),
+    graph_cost, acoustic_cost = the path's weight (float32), arcs = the path as indices into the dict's arc arrays,
+    final_state).  Only labels and weights go to the device; the strings are joined here."""
+    has_start = [int(c["n_states"]) > 0 and int(c.get("start", 0)) >= 0 for c in clats]    # :1055: no start state, empty path
+    csrs = [compact_lattice_to_csr(c) for c, ok in zip(clats, has_start) if ok]
+    if not csrs:
+        return [[None] * len(points) for _ in clats]
+    plen, paths, pfin, tg, ta = compact_lattice_best_paths_raw(csrs, points, workspace_limit)
+    empty = np.zeros(0, np.int32)
+    out = []
+    i = -1
+    for c, ok in zip(clats, has_start):
+        if not ok:
+            out.append([None] * len(points))
+            continue
+        i += 1
+        L = csrs[i]
+        row = []
+        for p in range(len(points)):
+            if plen[i, p] < 0:
+                row.append(None)
+                continue
+            arcs = L["perm"][paths[i][p]]
+            fs = int(L["state_of"][pfin[i, p]])
+            labels = np.asarray(c["arc_label"], np.int32)[arcs]
+            strings = [np.asarray(c["arc_string"][j], np.int32) for j in arcs] + [np.asarray(c["final_string"][fs], np.int32)]
+            row.append(dict(words=labels[labels != 0], alignment=np.concatenate(strings + [empty]).astype(np.int32),
+                            graph_cost=np.float32(tg[i, p]), acoustic_cost=np.float32(ta[i, p]), arcs=arcs.astype(np.int64),
+                            final_state=fs))
+        out.append(row)
+    return out
+
+
+def compact_lattice_best_paths_last_timings():
+    """Milliseconds the last compact_lattice_best_paths call of this thread spent in host preparation / upload / kernels /
+    download (the allocations and the host's scatter are in none of the four), in the whole C call, and the number of
+    kernel launches it took."""
+    ms = (C.c_float * 5)()
+    n = C.c_int32()
+    check(lib().kh_compact_lattice_best_paths_last_timings(ms, C.byref(n)))
+    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
+
+
 def rescore_lattice(lats, loglikes, utt_row_offsets, tid2pdf=None):
     """RescoreLattice (lat/lattice-functions.cc:1307-1358) for a batch: loglikes = device
     matrix (rows of lattice i at utt_row_offsets[i]...).  Returns the new arc_acoustic arrays."""

@@ -1236,12 +1236,13 @@ def write_compact_lattice(f, clat, binary=True):
     order = np.argsort(src, kind="stable")
     off = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]).astype(np.int64)
     inf = np.float32(np.inf)
+    start = int(clat.get("start", 0)) if n else -1      # (read_compact_lattice keeps the file's start state)
     if binary:
         def fst_str(x):
             return struct.pack("<i", len(x)) + x
         props = 0x1 | 0x2
         f.write(struct.pack("<i", _FST_MAGIC) + fst_str(b"vector") + fst_str(b"compactlattice44") + struct.pack("<ii", 2, 0) +
-                struct.pack("<Qqqq", props, 0 if n else -1, n, len(src)))
+                struct.pack("<Qqqq", props, start, n, len(src)))
 
         def weight(g, a, string):
             string = np.asarray(string, np.int32)
@@ -1260,7 +1261,8 @@ def write_compact_lattice(f, clat, binary=True):
 
     def wstr(g, a, string):
         return "%s,%s,%s" % (_fst_float(g), _fst_float(a), "_".join(str(int(x)) for x in string))
-    for st in range(n):
+    # FstPrinter: the start state's lines first, then the others in number order
+    for st in ([start] + [s for s in range(n) if s != start]) if start > 0 else range(n):
         for k in order[off[st]:off[st + 1]]:
             line = "%d\t%d\t%d" % (st, clat["arc_dst"][k], clat["arc_label"][k])
             if not (clat["arc_g"][k] == 0.0 and clat["arc_a"][k] == 0.0 and len(clat["arc_string"][k]) == 0):
@@ -1306,8 +1308,8 @@ def read_compact_lattice(s, binary=True):
                 asrc.append(st); adst.append(d); alab.append(il); ag.append(g); aa.append(a); astr.append(string)
         return dict(n_states=int(n), arc_src=np.array(asrc, np.int32), arc_dst=np.array(adst, np.int32),
                     arc_label=np.array(alab, np.int32), arc_g=np.array(ag, np.float32), arc_a=np.array(aa, np.float32),
-                    arc_string=astr, final_g=fg, final_a=fa, final_string=fs, complete=True)
-    arcs, finals, nstates = [], {}, 0
+                    arc_string=astr, final_g=fg, final_a=fa, final_string=fs, complete=True, start=int(start))
+    arcs, finals, nstates, start = [], {}, 0, None
 
     def weight(tok):
         parts = tok.split(",")
@@ -1337,6 +1339,8 @@ def read_compact_lattice(s, binary=True):
         else:
             finals[int(col[0])] = weight(col[1]) if len(col) > 1 else (0.0, 0.0, np.zeros(0, np.int32))
             nstates = max(nstates, int(col[0]) + 1)
+        if start is None:       # (the source state of the first line is the start state: FstCompiler)
+            start = int(col[0])
     fg = np.full(nstates, np.inf, np.float32)
     fa = np.full(nstates, np.inf, np.float32)
     fs = [np.zeros(0, np.int32) for _ in range(nstates)]
@@ -1345,7 +1349,7 @@ def read_compact_lattice(s, binary=True):
     return dict(n_states=nstates, arc_src=np.array([x[0] for x in arcs], np.int32), arc_dst=np.array([x[1] for x in arcs], np.int32),
                 arc_label=np.array([x[2] for x in arcs], np.int32), arc_g=np.array([x[3] for x in arcs], np.float32),
                 arc_a=np.array([x[4] for x in arcs], np.float32), arc_string=[x[5] for x in arcs], final_g=fg, final_a=fa,
-                final_string=fs, complete=True)
+                final_string=fs, complete=True, start=-1 if start is None else start)
 
 
 def write_fst(f, g):

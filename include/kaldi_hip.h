@@ -482,7 +482,7 @@ int kh_online_decoder_num_frames_decoded(const KhOnlineDecoder *dec, int stream,
  * Round 6, experimental: with KH_SERVE_LAZY_SPAN=n (default 0 = only when its arenas run low, the offline kernel's rule) a
  * stream also collects its garbage (PruneActiveTokens + compaction) once n frames have gone unpruned, so that no chunk of a
  * long utterance waits for the collection of a backlog of thousands of frames (chunk latency max 113 -> 28 ms at n = 128);
- * off by default: the serving stress harness saw rare GPU faults with it on (csrc/kh_decoder.hip OnlineLazySpan). */
+ * off by default: the serving stress harness saw rare GPU faults with it on (csrc/kh_decoder_host.hip OnlineLazySpan). */
 int kh_online_decoder_set_lazy_prune(KhOnlineDecoder *dec, int enable);
 /* kh_decoder_set_reference_order for the streams: LatticeFasterOnlineDecoder::ProcessEmitting (decoder/lattice-faster-online-
  * decoder.cc:864-951) walks the same HashList against the same running next_cutoff as the offline decoder, and with this set

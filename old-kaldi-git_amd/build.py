@@ -23,6 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # the kernel's entry - far more values than the 64-register budget holds, so they are spilled there and reloaded from scratch
 # at every use (round 5: kernel-resource-usage ScratchSize 132 -> 84 B per lane for the canonical kernel, 304 -> 204 for the
 # reference-order one with the pass off; same-box A/B 554 -> 545 ms and 1210 -> 1167 ms, bit-identical results).
+# (kh_decoder.hip is the decoder's device code; its host half, kh_decoder_host.hip, holds no kernel and takes the common flags.)
 EXTRA = {"kh_decoder.hip": ["-mllvm", "-disable-machine-licm"]}
 
 

@@ -42,3 +42,10 @@ def test_decode_kernel_spill_budget():
     # counters in LDS, a lane index re-made at every use in the list-order routines; 981 -> 903 -> 856 ms on one box)
     assert rows[key_x][5] <= 144 and rows[key_x][3] <= 40, "DecodeKernel<1,1> scratch %d B, %d scratch loads" % (rows[key_x][5], rows[key_x][3])
     assert dpp >= 200 and bpermute <= 40, "the wave scans are expected on DPP, not on ds_bpermute (%d DPP, %d bpermute)" % (dpp, bpermute)
+    # the online and serving kernels (the same phases behind a launch per chunk / a resident workgroup per stream).  Pinned when
+    # the host code left this file: scratch bytes as measured then, rounded up to a multiple of 8; static scratch loads + 10 %.
+    for name, max_bytes, max_loads, was in (("OnlineKernel<true>", 120, 33, "116 B / 30 loads"), ("OnlineKernel<false>", 0, 0, "0 B / 0 loads"),
+                                            ("ServeKernel<true>", 112, 71, "112 B / 65 loads"), ("ServeKernel<false>", 0, 0, "0 B / 0 loads")):
+        row = rows[next(k for k in rows if name in k)]
+        assert row[5] <= max_bytes and row[3] <= max_loads, "%s scratch %d B, %d scratch loads (%s when the decoder's host code was split off)" % (
+            name, row[5], row[3], was)

@@ -33,6 +33,6 @@ s = s.replace('#include "kh_common.h"', '#include "/root/repo/old-kaldi-git_amd/
 open(b, "w").write(s)
 PY
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-result -D__HIP_PLATFORM_AMD__ -mllvm -amdgpu-inline-max-bb=100000 -I$P/csrc -Iinclude -c $src -o /tmp/kh_decoder_$name.o
-objs=$(ls $P/build/*.o | grep -v kh_decoder.o)
+objs=$(ls $P/build/*.o | grep -v '/kh_decoder\.o$')   # (the host half, build/kh_decoder_host.o, is linked as built: no flags here)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/libkh_exp_$name.so $objs /tmp/kh_decoder_$name.o
 echo tools/libkh_exp_$name.so

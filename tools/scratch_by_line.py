@@ -30,10 +30,14 @@ def main():
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     cur = 0
     ld, st, ins = collections.Counter(), collections.Counter(), collections.Counter()
+    # line numbers are kh_decoder.hip's: code inlined from a header (kh_decoder_types.h: Arr<T>, Load4* / Store4*) stays with the
+    # line of the kernel file that was current when it was reached
+    own = {m.group(1) for m in (re.match(r"\s+\.file\s+(\d+)\s.*kh_decoder\.hip\"", l) for l in lines) if m}
     for l in lines[start:end]:
-        m = re.match(r"\s+\.loc\s+\d+\s+(\d+)", l)
+        m = re.match(r"\s+\.loc\s+(\d+)\s+(\d+)", l)
         if m:
-            cur = int(m.group(1)) // bucket * bucket
+            if not own or m.group(1) in own:
+                cur = int(m.group(2)) // bucket * bucket
             continue
         m = re.match(r"\s+([a-z_0-9]+)\s", l)
         if m:

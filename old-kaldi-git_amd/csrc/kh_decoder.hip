@@ -3299,14 +3299,16 @@ __device__ int OrderFrontierLds(const Utt &u, const Params &p, int nb, int fe, i
   }
   LdsSync();
   int n_b2;   // buckets with more than one token
+  uint32_t pre2 = 0u;   // set bits in front of the shared-bucket bitmap: P2[w] - pre2 = the prefix counts of its bits alone
   if (comb) {
     const int n_bits = BitmapPrefix(K, P, W1, sh);
     LdsSync();
-    const int pre2 = static_cast<int>(P[o2]);
-    n_b2 = n_bits - pre2;
-    LdsSync();   // (every lane has read P[o2] = P2[0] before it is rewritten)
-    for (int w = tid; w < Hw; w += NT) P2[w] -= static_cast<uint32_t>(pre2);   // (prefix counts of the shared-bucket bits alone)
-    LdsSync();
+    // P2 is NOT rebased in place (round 7: that was a pass over Hw words between two barriers of its own).  P[0, W1) was
+    // written by BitmapPrefix in front of the barrier above and is only read from here on - by this line, by BitRank and
+    // at P2's single use in step 4, where pre2 is subtracted - until the barrier behind step 4 lets T's rewrite and the
+    // bucket counts reuse the area.
+    pre2 = Uni(P[o2]);
+    n_b2 = n_bits - static_cast<int>(pre2);
   } else {
     n_b2 = BitmapPrefix(K + o2, P2, Hw, sh);
     LdsSync();
@@ -3325,7 +3327,7 @@ __device__ int OrderFrontierLds(const Utt &u, const Params &p, int nb, int fe, i
     const uint32_t bits2 = K[o2 + (bk >> 5)];
     uint32_t word = 0u;
     if (i < n_emit) word = comb ? static_cast<uint32_t>(BitRank(K, P, UX(x_q)[i])) : t0 >> 17;
-    if ((bits2 & m) != 0u) word |= ((P2[bk >> 5] + static_cast<uint32_t>(__popc(bits2 & (m - 1u)))) << 13) | (1u << 26);
+    if ((bits2 & m) != 0u) word |= ((P2[bk >> 5] - pre2 + static_cast<uint32_t>(__popc(bits2 & (m - 1u)))) << 13) | (1u << 26);
     else if (i >= n_emit) cb[k] = static_cast<int>(bk);
     tw[k] = word;
   }
@@ -3376,9 +3378,11 @@ __device__ int OrderFrontierLds(const Utt &u, const Params &p, int nb, int fe, i
       T[i] = hm | (static_cast<uint32_t>(inb & 255) << 13);
     }
     if (wide) sh->flag = 1;
-  } else {
-    LdsSync();
   }
+  // ONE barrier on either path (round 7: a frame without shared buckets had two in a row here).  In front of it: T's and
+  // Cb's words of step 4 (n_b2 == 0: final as they are), or step 5's rewrite of T by the lane that owns the word, and the
+  // flag's only writers so far.  Behind it: the closure section and the position counts read T words of other lanes and
+  // overwrite K[0, 7168), which step 5 has finished reading (K[d], M16).
   LdsSync();
   if (Uni(sh->flag) != 0) return 2;   // (a bucket of more than 255 tokens)
   SubStamp(u, sh, 48);
@@ -3500,6 +3504,8 @@ __device__ int OrderFrontierLds(const Utt &u, const Params &p, int nb, int fe, i
     if (u.phase_cycles != nullptr && tid == 0) sh->phase[64] += 1;
     // ---- 7. the closure's tokens: ranks; bucket mates among themselves (shared bucket: behind its tokens of the emitting pass)
     if (tid < n_new) Cr[tid] = static_cast<uint32_t>(n_emit + my_rank);
+    // (this barrier also orders every wave's test of the flag above before step 7's store to it below: without it a wave
+    // could see a flag that step 7 of a faster wave has set, leave here, and run one barrier apart from the others)
     LdsSync();
     if (tid < n_new) {
       const int i = n_emit + tid;
@@ -3525,7 +3531,11 @@ __device__ int OrderFrontierLds(const Utt &u, const Params &p, int nb, int fe, i
   }
   SubStamp(u, sh, 50);
   // ---- 8. positions: tokens per first-of-bucket rank, one scan over the rank space, + the rank inside the bucket
-  LdsSync();
+  // No barrier in front of the zero fill (round 7).  K's last readers are behind a barrier already on both paths: with a
+  // closure, step 7's reads of Cb / Cr (and everything of step 6) lie in front of the barrier that publishes its flag, and
+  // what follows it touches T only; without one, step 5's reads of K[d] and the 16-bit ranks lie in front of the barrier
+  // at the end of step 5.  The barrier BEHIND the fill also orders step 7's rewrite of T[n_emit + tid] (lane tid) before
+  // the counts below, which read that word from lane (n_emit + tid) % NT.
   for (int w = tid; w < n; w += NT) K[w] = 0u;
   LdsSync();
   for (int i = tid; i < n; i += NT) (void)__hip_atomic_fetch_add(&K[T[i] & 0x1fffu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -3912,22 +3922,24 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
     constexpr int kPer = kLdsSlots / NT;
     static_assert(kPer == 8, "a lane's positions are one byte of the bitmap");
     const int w0 = tid * kPer;
-    uint32_t mm[kPer], lane_min = 0xFFFFFFFFu;
+    // A position's M is NOT kept across the scan's barrier (round 7): the few positions whose bit is set read x_m again
+    // behind it (nothing writes x_m between the sweep and the loop that takes the results back).  Eight M words next to
+    // the eight counts did not fit the 64 registers around the scan's sixteen-wave loop and went through scratch.
+    uint32_t lane_min = 0xFFFFFFFFu;
     int cc[kPer], lane_sum = 0;
     const uint32_t bits = w0 < n ? (K[n + (w0 >> 5)] >> (w0 & 31)) & 0xffu : 0u;
 #pragma unroll
     for (int j = 0; j < kPer; j++) {
       const uint32_t kv = K[w0 + j];   // (unguarded: inside the area)
       cc[j] = w0 + j < n ? static_cast<int>(kv) : 0;
-      mm[j] = 0xFFFFFFFFu;
       lane_sum += cc[j];
     }
     if (bits != 0u) {   // (rare: a token with arcs under the bound of its run)
 #pragma unroll
       for (int j = 0; j < kPer; j++)
         if (((bits >> j) & 1u) != 0u) {
-          mm[j] = xp_m[w0 + j];
-          lane_min = mm[j] < lane_min ? mm[j] : lane_min;
+          const uint32_t m = xp_m[w0 + j];
+          lane_min = m < lane_min ? m : lane_min;
         }
     }
     int ex_sum, tot_sum;
@@ -3938,7 +3950,10 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
 #pragma unroll
     for (int j = 0; j < kPer; j++) {
       if (w0 + j < n) { V[w0 + j] = rm; K[w0 + j] = static_cast<uint32_t>(rs); }
-      rm = mm[j] < rm ? mm[j] : rm;
+      if (((bits >> j) & 1u) != 0u) {
+        const uint32_t m = xp_m[w0 + j];
+        rm = m < rm ? m : rm;
+      }
       rs += cc[j];
     }
     run_min = run_min < tot_min ? run_min : tot_min;
@@ -3950,24 +3965,28 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
     constexpr int kPer = 2 * kLdsSlots / NT;
     static_assert(kPer == 16, "a lane's positions are half a word of the bitmap");
     const int w0 = tid * kPer;
-    uint32_t mm[kPer], lane_min = 0xFFFFFFFFu;
-    int cc[kPer], lane_sum = 0;
+    // Across the scan's barrier a lane keeps its sixteen counts as the eight 16-bit PAIRS they arrive in (positions at or
+    // beyond n masked to zero) and no M at all: the few positions whose bit is set read x_m again behind the barrier
+    // (round 7; nothing writes x_m before the loop that takes the results back, and the steps below go to x_c / x_h).  As
+    // sixteen counts + sixteen M words the lane's state was 32 registers of a budget of 64, and 28 of them went through
+    // scratch around the scan's sixteen-wave loop - all but two of the kernel's static scratch loads, in the 29 % of the
+    // benchmark's frames that take this tier.
+    uint32_t lane_min = 0xFFFFFFFFu;
+    uint32_t cp[kPer / 2];
+    int lane_sum = 0;
     const uint32_t bits = w0 < n ? (V[kMidBitBase + (w0 >> 5)] >> (w0 & 31)) & 0xffffu : 0u;
 #pragma unroll
     for (int j = 0; j < kPer / 2; j++) {
       const uint32_t kv = K[(w0 >> 1) + j];   // (unguarded: inside the area)
-      cc[2 * j] = w0 + 2 * j < n ? static_cast<int>(kv & 0xffffu) : 0;
-      cc[2 * j + 1] = w0 + 2 * j + 1 < n ? static_cast<int>(kv >> 16) : 0;
-      lane_sum += cc[2 * j] + cc[2 * j + 1];
+      cp[j] = (w0 + 2 * j < n ? kv & 0xffffu : 0u) | (w0 + 2 * j + 1 < n ? kv & 0xffff0000u : 0u);
+      lane_sum += static_cast<int>(cp[j] & 0xffffu) + static_cast<int>(cp[j] >> 16);
     }
-#pragma unroll
-    for (int j = 0; j < kPer; j++) mm[j] = 0xFFFFFFFFu;
     if (bits != 0u) {   // (rare: a token with arcs under the bound of its run)
 #pragma unroll
       for (int j = 0; j < kPer; j++)
         if (((bits >> j) & 1u) != 0u) {
-          mm[j] = xp_m[w0 + j];
-          lane_min = mm[j] < lane_min ? mm[j] : lane_min;
+          const uint32_t m = xp_m[w0 + j];
+          lane_min = m < lane_min ? m : lane_min;
         }
     }
     int ex_sum, tot_sum;
@@ -3979,13 +3998,16 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
     for (int j = 0; j < kPer; j++) {
       const int w = w0 + j;
       if (w < n) { if (w < kLdsSlots) K[w] = static_cast<uint32_t>(rs); else V[w - kLdsSlots] = static_cast<uint32_t>(rs); }
-      if (mm[j] < rm) {   // the running cutoff drops behind this position
-        rm = mm[j];
-        const int at = __hip_atomic_fetch_add(&sh->x_nbp, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        xp_c[at] = w + 1;                               // (first position the new value holds for)
-        UX(x_h)[at] = static_cast<int32_t>(rm);
+      if (((bits >> j) & 1u) != 0u) {
+        const uint32_t m = xp_m[w];
+        if (m < rm) {   // the running cutoff drops behind this position
+          rm = m;
+          const int at = __hip_atomic_fetch_add(&sh->x_nbp, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          xp_c[at] = w + 1;                               // (first position the new value holds for)
+          UX(x_h)[at] = static_cast<int32_t>(rm);
+        }
       }
-      rs += cc[j];
+      rs += static_cast<int>((cp[j >> 1] >> (16 * (j & 1))) & 0xffffu);
     }
     run_min = run_min < tot_min ? run_min : tot_min;
     run_sum = tot_sum;

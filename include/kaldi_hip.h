@@ -721,6 +721,40 @@ int kh_compact_lattice_best_paths(int n_lats, const int32_t *lat_state_offsets, 
 int kh_compact_lattice_best_paths_set_workspace_limit(size_t bytes);
 int kh_compact_lattice_best_paths_last_timings(float *ms5, int32_t *n_launches);
 
+/* PruneLattice<CompactLattice> (lat/lattice-functions.cc:186-265) for a batch of top-sorted CompactLattices and n_points
+ * score points in one call (csrc/kh_latprune.hip): what `lattice-scale | lattice-add-penalty | lattice-prune --beam=B`
+ * (latbin/lattice-prune.cc:87) decides once per point of a scoring grid.  HOST CSR, scales and penalties as
+ * kh_compact_lattice_best_paths; lat_start[l] = lat->Start() (:201) in the lattice's own numbering - the states in front of
+ * it are unreachable, unlike the best-path search, which starts at state 0; beams[p] = the point's float beam.  Per
+ * lattice and point, in the reference's order: the point applied to arc and final weights as kh_compact_lattice_best_paths
+ * applies it (fstext/lattice-weight.h:233-241, lattice-functions.cc:1140-1143, cost = (double)g' + (double)a'); the
+ * Viterbi forward sweep :211-229; cutoff = best_final_cost + (double)beam :231; the backward sweep :239-262 with its three
+ * comparisons as written there (a final weight is cleared when backward + forward > cutoff and it is not +inf; an arc is
+ * pruned when this_forward_cost + (arc_cost + backward_cost[next]) > cutoff, in that association; arc_backward_cost <
+ * this_backward_cost); then fst::Connect :263, computed: a state survives when it is reachable from the start state over
+ * unpruned arcs and reaches a state that kept its final weight, an arc when it is unpruned and both its ends survive.
+ * Outputs (HOST) are bit masks over the points, W = ceil(n_points / 64) words per arc or state, bit p % 64 of word p / 64
+ * for point p: arc_keep[a W + w] (the arc is in the pruned, connected lattice), state_keep[s W + w] (the state survives
+ * Connect), final_keep[s W + w] (the state keeps its final weight), and best_final_cost[l n_points + p] (:208-229; +inf =
+ * no final state is reachable: nothing is pruned and everything is disconnected).  The sweeps only take minima, which do
+ * not depend on the order of the candidates as long as none is NaN or -inf, so the results equal the reference's bit for
+ * bit; weights that are NaN or -inf are refused.  KH_EINVAL, with the arc, state or point named, for an arc to a state that
+ * is not higher-numbered (:193, :218), lat_start out of range, beam <= 0 (:192), n_points < 1, a NaN or -inf weight.
+ * The workspace is n_states x 8 bytes x 64 W per lattice in flight; lattices are taken longest first, as many per launch
+ * as half of the free device memory admits, or as kh_compact_lattice_prune_set_workspace_limit(bytes) admits: a setting
+ * of the CALLING THREAD (0 = back to automatic; one lattice always runs).  kh_compact_lattice_prune_last_timings:
+ * milliseconds the last call of this thread spent in { host preparation (validation, incoming-arc lists), upload, kernels,
+ * download (HIP events; the allocations are in none of the four), the whole call by the host's clock }, and its number of
+ * launches of the sweep kernel (may be NULL). */
+int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start,
+                             const int64_t *arc_offsets, const int32_t *arc_label, const int32_t *arc_nextstate,
+                             const float *arc_graph, const float *arc_acoustic, const float *final_graph,
+                             const float *final_acoustic, int n_points, const double *scales, const float *penalties,
+                             const float *beams, uint64_t *arc_keep, uint64_t *state_keep, uint64_t *final_keep,
+                             double *best_final_cost);
+int kh_compact_lattice_prune_set_workspace_limit(size_t bytes);
+int kh_compact_lattice_prune_last_timings(float *ms5, int32_t *n_launches);
+
 /* LatticeForwardBackwardMpeVariants (lat/lattice-functions.cc:740-919): criterion
  * "smbr" (is_mpfe = 0) or "mpfe".  tid2phone / tid2pdf = TransitionIdToPhone /
  * TransitionIdToPdf as arrays of num_tids + 1 entries indexed by transition-id;

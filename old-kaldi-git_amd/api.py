@@ -1453,6 +1453,189 @@ def compact_lattice_best_paths_last_timings():
     return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
 
 
+# ---------------------------------------------------------------- pruning over score points (csrc/kh_latprune.hip)
+def compact_lattice_prune_order(clat):
+    """The state numbering PruneLattice works in (lat/lattice-functions.cc:193-198): None when the lattice has OpenFst's
+    kTopSorted property - every arc goes to a higher-numbered state, WHATEVER the start state is (:199-201 then takes
+    lat->Start() and leaves the states in front of it unreachable) - else order[old] = new of fst::TopSort, as
+    compact_lattice_top_order numbers.  Raises on a cycle (:194-196)."""
+    n = int(clat["n_states"])
+    start = int(clat.get("start", 0))
+    if n == 0 or start < 0:
+        return None
+    if start >= n:
+        raise KhError("compact lattice: start state %d of %d states" % (start, n))
+    if bool(np.all(np.asarray(clat["arc_dst"], np.int64) > np.asarray(clat["arc_src"], np.int64))):
+        return None
+    return compact_lattice_top_order(clat)
+
+
+def compact_lattice_to_prune_csr(clat):
+    """compact_lattice_to_csr in compact_lattice_prune_order's numbering, plus start = the start state in that numbering."""
+    n = int(clat["n_states"])
+    src, dst = np.asarray(clat["arc_src"], np.int64), np.asarray(clat["arc_dst"], np.int64)
+    order = compact_lattice_prune_order(clat)
+    state_of = np.arange(n, dtype=np.int64)
+    start = int(clat.get("start", 0))
+    if order is not None:
+        src, dst = order[src], order[dst]
+        state_of = np.argsort(order)
+        start = int(order[start])
+    perm = np.argsort(src, kind="stable")
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(np.bincount(src, minlength=n))
+    return dict(n_states=n, start=start, arc_offsets=off, arc_label=np.asarray(clat["arc_label"], np.int32)[perm],
+                arc_nextstate=dst[perm].astype(np.int32), arc_graph=np.asarray(clat["arc_g"], np.float32)[perm],
+                arc_acoustic=np.asarray(clat["arc_a"], np.float32)[perm],
+                final_graph=np.asarray(clat["final_g"], np.float32)[state_of],
+                final_acoustic=np.asarray(clat["final_a"], np.float32)[state_of], perm=perm, state_of=state_of)
+
+
+def _point_beams(beams, K):
+    b = np.asarray(beams, np.float32).reshape(-1)
+    if b.size == 1:
+        b = np.repeat(b, K)
+    if b.size != K:
+        raise KhError("compact_lattice_prune: %d beams for %d score points" % (b.size, K))
+    return np.ascontiguousarray(b)
+
+
+def compact_lattice_prune_raw(csrs, starts, points, beams, workspace_limit=None):
+    """kh_compact_lattice_prune on CSR dicts (compact_lattice_to_prune_csr's layout, top-sorted), starts = the start state
+    of each, points as compact_lattice_best_paths_raw takes them, beams = one float or one per point.  Returns
+    dict(arc_keep, state_keep, final_keep = bool [arcs or states of the whole batch x n_points], best_final_cost
+    [n_lats x n_points], state_offsets, arc_offsets = where each lattice's rows begin).  workspace_limit as
+    compact_lattice_best_paths_raw's."""
+    n, K = len(csrs), len(points)
+    if n == 0 or K == 0:
+        raise KhError("compact_lattice_prune: no lattices or no score points")
+    soff = np.zeros(n + 1, np.int32)
+    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
+    aoff, lat_arc_off = [np.zeros(1, np.int64)], np.zeros(n + 1, np.int64)
+    for i, L in enumerate(csrs):
+        o = np.asarray(L["arc_offsets"], np.int64)
+        aoff.append(o[1:] + lat_arc_off[i])
+        lat_arc_off[i + 1] = lat_arc_off[i] + int(o[-1])
+    aoff = np.ascontiguousarray(np.concatenate(aoff))
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt) for L in csrs]))
+    lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
+    g, a = cat("arc_graph", np.float32), cat("arc_acoustic", np.float32)
+    fg, fa = cat("final_graph", np.float32), cat("final_acoustic", np.float32)
+    st = np.ascontiguousarray(np.asarray(starts, np.int32).reshape(n))
+    scales = np.ascontiguousarray(np.stack([np.asarray(s, np.float64).reshape(4) for s, _ in points]))
+    pens = np.ascontiguousarray(np.asarray([p for _, p in points], np.float32))
+    bm = _point_beams(beams, K)
+    S, A, W = int(soff[-1]), int(lat_arc_off[-1]), (K + 63) // 64
+    akeep, skeep, fkeep = np.zeros((A, W), np.uint64), np.zeros((S, W), np.uint64), np.zeros((S, W), np.uint64)
+    best = np.empty((n, K), np.float64)
+    ip, fp, up = capi.c_int32_p, capi.c_float_p, capi.c_uint64_p
+    if workspace_limit is not None:
+        check(lib().kh_compact_lattice_prune_set_workspace_limit(int(workspace_limit)))
+    try:
+        check(lib().kh_compact_lattice_prune(
+            n, soff.ctypes.data_as(ip), st.ctypes.data_as(ip), aoff.ctypes.data_as(capi.c_int64_p), lab.ctypes.data_as(ip),
+            ns.ctypes.data_as(ip), g.ctypes.data_as(fp), a.ctypes.data_as(fp), fg.ctypes.data_as(fp), fa.ctypes.data_as(fp), K,
+            scales.ctypes.data_as(capi.c_double_p), pens.ctypes.data_as(fp), bm.ctypes.data_as(fp), akeep.ctypes.data_as(up),
+            skeep.ctypes.data_as(up), fkeep.ctypes.data_as(up), best.ctypes.data_as(capi.c_double_p)))
+    finally:
+        if workspace_limit is not None:
+            check(lib().kh_compact_lattice_prune_set_workspace_limit(0))
+    # bit p % 64 of word p / 64 -> column p (the words are little-endian: byte p / 8, bit p % 8)
+    bits = lambda m: np.unpackbits(m.astype("<u8").view(np.uint8).reshape(len(m), 8 * W), axis=1, bitorder="little")[:, :K].astype(bool)
+    return dict(arc_keep=bits(akeep), state_keep=bits(skeep), final_keep=bits(fkeep), best_final_cost=best,
+                state_offsets=soff.astype(np.int64), arc_offsets=lat_arc_off)
+
+
+def _apply_score_point(g, a, label, scale, penalty):
+    """ScaleTupleWeight (fstext/lattice-weight.h:233-241) then, with a label array, the penalty on arcs with a word
+    (lat/lattice-functions.cc:1140-1143) on float32 arrays: what csrc/kh_latprune.hip applies to a weight."""
+    s = np.asarray(scale, np.float64).reshape(4)
+    zero = g == np.float32(np.inf)
+    g64, a64 = np.where(zero, 0.0, g.astype(np.float64)), np.where(zero, 0.0, a.astype(np.float64))
+    inf = np.float32(np.inf)
+    with np.errstate(all="ignore"):
+        g2 = np.where(zero, inf, (s[0] * g64 + s[1] * a64).astype(np.float32)).astype(np.float32)
+        a2 = np.where(zero, inf, (s[2] * g64 + s[3] * a64).astype(np.float32)).astype(np.float32)
+        if label is not None:
+            g2 = np.where(label != 0, g2 + np.float32(penalty), g2).astype(np.float32)
+    return g2, a2
+
+
+def _empty_pruned():
+    z, f = np.zeros(0, np.int32), np.zeros(0, np.float32)
+    return dict(n_states=0, start=-1, arc_src=z, arc_dst=z, arc_label=z, arc_g=f, arc_a=f, arc_string=[], final_g=f, final_a=f,
+                final_string=[], complete=True, kept_states=np.zeros(0, np.int64), kept_arcs=np.zeros(0, np.int64),
+                final_kept=np.zeros(0, bool), ok=False)
+
+
+def compact_lattice_prune(clats, points, beams, workspace_limit=None):
+    """lattice-scale | lattice-add-penalty | lattice-prune --beam=B (PruneLattice, lat/lattice-functions.cc:186-265) for a
+    batch of CompactLattices (dict layout of kaldi_io.read_compact_lattice) and a list of score points (score_point) in ONE
+    device call; beams = one float or one per point.  Returns per lattice a list over the points of a CompactLattice dict in
+    the same layout: the surviving states renumbered densely in the top-sorted order (what DeleteStates leaves; the start
+    state becomes the first survivor), the surviving arcs in their order within a state, the weights those AFTER the point
+    (what the pipe carries into lattice-prune), the strings untouched.  Each dict also carries kept_states, kept_arcs
+    (indices into the input dict, in the output's order), final_kept (per surviving state) and ok; ok is False when nothing
+    survives - PruneLattice returns false - and the dict then has n_states = 0 and start = -1.  A lattice without states or
+    without a start state gives that for every point, without a device call."""
+    K = len(points)
+    has_start = [int(c["n_states"]) > 0 and int(c.get("start", 0)) >= 0 for c in clats]    # :203
+    csrs = [compact_lattice_to_prune_csr(c) for c, ok in zip(clats, has_start) if ok]
+    if not csrs:
+        return [[_empty_pruned() for _ in range(K)] for _ in clats]
+    raw = compact_lattice_prune_raw(csrs, [L["start"] for L in csrs], points, beams, workspace_limit)
+    soff, aoff = raw["state_offsets"], raw["arc_offsets"]
+    inf, empty = np.float32(np.inf), np.zeros(0, np.int32)
+    out = []
+    i = -1
+    for c, ok in zip(clats, has_start):
+        if not ok:
+            out.append([_empty_pruned() for _ in range(K)])
+            continue
+        i += 1
+        L = csrs[i]
+        n = L["n_states"]
+        ak, sk, fk = (raw["arc_keep"][aoff[i]:aoff[i + 1]], raw["state_keep"][soff[i]:soff[i + 1]],
+                      raw["final_keep"][soff[i]:soff[i + 1]])
+        src = np.repeat(np.arange(n, dtype=np.int64), np.diff(L["arc_offsets"]))
+        dst = L["arc_nextstate"].astype(np.int64)
+        astr = np.empty(len(src), object)
+        for j, x in enumerate(c["arc_string"]):
+            astr[j] = x
+        fstr = np.empty(n, object)
+        for s, x in enumerate(c["final_string"]):
+            fstr[s] = x
+        row = []
+        for p, (scale, pen) in enumerate(points):
+            ks = np.flatnonzero(sk[:, p])
+            if len(ks) == 0:
+                row.append(_empty_pruned())
+                continue
+            ka = np.flatnonzero(ak[:, p])
+            new = np.cumsum(sk[:, p]) - 1
+            g, a = _apply_score_point(L["arc_graph"][ka], L["arc_acoustic"][ka], L["arc_label"][ka], scale, pen)
+            fg, fa = _apply_score_point(L["final_graph"][ks], L["final_acoustic"][ks], None, scale, pen)
+            kept = fk[ks, p]
+            kept_states, kept_arcs = L["state_of"][ks], L["perm"][ka]
+            row.append(dict(n_states=len(ks), start=int(new[L["start"]]), arc_src=new[src[ka]].astype(np.int32),
+                            arc_dst=new[dst[ka]].astype(np.int32), arc_label=L["arc_label"][ka], arc_g=g, arc_a=a,
+                            arc_string=astr[kept_arcs].tolist(), final_g=np.where(kept, fg, inf).astype(np.float32),
+                            final_a=np.where(kept, fa, inf).astype(np.float32),
+                            final_string=[x if k else empty for x, k in zip(fstr[kept_states].tolist(), kept.tolist())],
+                            complete=True, kept_states=kept_states, kept_arcs=kept_arcs, final_kept=kept, ok=True))
+        out.append(row)
+    return out
+
+
+def compact_lattice_prune_last_timings():
+    """Milliseconds the last compact_lattice_prune call of this thread spent in host preparation / upload / kernels /
+    download (the allocations are in none of the four), in the whole C call, and the number of launches of the sweep kernel."""
+    ms = (C.c_float * 5)()
+    n = C.c_int32()
+    check(lib().kh_compact_lattice_prune_last_timings(ms, C.byref(n)))
+    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
+
+
 def rescore_lattice(lats, loglikes, utt_row_offsets, tid2pdf=None):
     """RescoreLattice (lat/lattice-functions.cc:1307-1358) for a batch: loglikes = device
     matrix (rows of lattice i at utt_row_offsets[i]...).  Returns the new arc_acoustic arrays."""

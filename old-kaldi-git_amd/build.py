@@ -27,6 +27,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 EXTRA = {"kh_decoder.hip": ["-mllvm", "-disable-machine-licm"]}
 
 
+def flags_for(src):
+    """The compiler flags of one csrc file (tools/isa_mix.py and tools/build_variant*.sh take them from here)."""
+    return FLAGS + EXTRA.get(os.path.basename(src), [])
+
+
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
@@ -53,7 +58,7 @@ def build(force=False, verbose=False, jobs=8):
         if (not force and os.path.exists(obj) and os.path.getmtime(obj) > os.path.getmtime(src)
                 and os.path.getmtime(obj) > hdr_t):
             continue
-        cmd = [HIPCC] + FLAGS + EXTRA.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
+        cmd = [HIPCC] + flags_for(src) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((src, subprocess.Popen(cmd)))

@@ -37,6 +37,13 @@
 // ArcPdfKernel) and, at the end, one plain host launcher per kernel family.  The structs and constants the kernels share
 // with the host are in kh_decoder_types.h; KhDecoder / KhOnlineDecoder, the arenas, the lattices, the worker threads, the
 // environment switches and the kh_fst_* / kh_decoder_* / kh_online_decoder_* C API are in kh_decoder_host.hip.
+//
+// Compile-time switches (DESIGN.md "Source layout" has the list with what each is for): the launch shape KH_NT, KH_NPH,
+// KH_COMPACT_EVERY, KH_WG_PER_CU (kh_decoder_types.h, shared with the host file), the debug builds KH_BOUNDS_CHECK,
+// KH_BARRIER_CHECK, KH_SERVE_MARKERS (tools/build_variant.sh) and the fine stamps KH_X_STAMPS.  Nothing else: the A/B
+// experiments of rounds 4-7 that lost are gone from the source - their verdicts stand as comments where they explain the
+// code that is there, and NOTEBOOK.md section 12 lists every one with the commit that still holds the other branch.  The
+// tests reach the list-order tiers through the run-time KH_DECODER_* switches of the host file.
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
@@ -63,11 +70,7 @@ __device__ __forceinline__ unsigned KhOpaqueTidX() {
   asm volatile("" : "+v"(t));
   return t;
 }
-#ifndef KH_PLAIN_TID
 #define KH_TIDX (KhOpaqueTidX())
-#else
-#define KH_TIDX (threadIdx.x)
-#endif
 
 // -DKH_SERVE_MARKERS (debug builds): thread 0 of a serving workgroup leaves (place << 24 | detail) in its stream's control
 // block in host memory as it goes; a KH_ETIMEOUT dump then says WHERE a workgroup that never came back is (round 6: one
@@ -89,6 +92,9 @@ __device__ int32_t *g_wave_mark = nullptr;
 constexpr int EU = 2;              // chunks of NT tokens an expansion group scans per barrier (2: -1 %; 4 spills)
 constexpr int KC = 4;              // chunks of NT slots the compaction moves per barrier when the slide has opened a gap
 constexpr int PU = 1;              // token / link slots a lane keeps in flight per round of a sweep (measured: 1 beats 2, 4, 8 - the sweeps are bound by the CU's address pipeline, not by latency, and more slots spill)
+constexpr int kPartCand = 11000;   // accepted candidates per part of pass 2 (7 k / 9 k / 13 k / 15 k measured: +6 % / 0 / +1 % / +8 %)
+constexpr int kLocBits = 5;        // pass 2's token table is hashed by blocks of 2^kLocBits consecutive state ids (EmitPass2, LOCALITY)
+constexpr int kLocShift = 1;       // ... of which a state id drops its low kLocShift bits first (a state's record spans ~3 units)
 
 // Token costs are updated with L2 atomics (atomicMin), which do not refresh this
 // CU's vector L1: a plain load could return a stale L1 copy of the line (e.g. one
@@ -128,57 +134,26 @@ __device__ __forceinline__ void LaunderOne(T &x) {
   else asm volatile("s_mov_b32 %0, %1" : "=s"(y) : "s"(x));
   x = y;
 }
-#ifndef KH_NO_LAUNDER
-#define KH_LAUNDER(x) LaunderOne(x)
-#else
-#define KH_LAUNDER(x) do {} while (0)
-#endif
-// per-phase switches of the local copies (same-box A/B builds)
-#ifdef KH_NO_P2_LOCAL
-#define KH_LAUNDER_P2(x) do {} while (0)
-#else
-#define KH_LAUNDER_P2(x) KH_LAUNDER(x)
-#endif
-#ifdef KH_NO_GC_LOCAL
-#define KH_LAUNDER_GC(x) do {} while (0)
-#else
-#define KH_LAUNDER_GC(x) KH_LAUNDER(x)
-#endif
-#ifdef KH_NO_NE_LOCAL
-#define KH_LAUNDER_NE(x) do {} while (0)
-#else
-#define KH_LAUNDER_NE(x) KH_LAUNDER(x)
-#endif
-#ifdef KH_NO_FB_LOCAL
-#define KH_LAUNDER_FB(x) do {} while (0)
-#else
-#define KH_LAUNDER_FB(x) KH_LAUNDER(x)
-#endif
-#ifdef KH_NO_X_LOCAL
-#define KH_LAUNDER_X(x) do {} while (0)
-#else
-#define KH_LAUNDER_X(x) KH_LAUNDER(x)
-#endif
 __device__ __forceinline__ void Launder(Utt &u) {
-  KH_LAUNDER(u.ll); KH_LAUNDER(u.ll_stride); KH_LAUNDER(u.T); KH_LAUNDER(u.tok_cap);
-  KH_LAUNDER(u.tok_state.p); KH_LAUNDER(u.tok_cost.p); KH_LAUNDER(u.tok_extra.p);
-  KH_LAUNDER(u.link_cap);
-  KH_LAUNDER(u.link_dst.p); KH_LAUNDER(u.link_arc.p); KH_LAUNDER(u.link_src.p); KH_LAUNDER(u.link_k.p); KH_LAUNDER(u.link_a.p);
-  KH_LAUNDER(u.frame_b.p); KH_LAUNDER(u.frame_e.p); KH_LAUNDER(u.feps_b.p); KH_LAUNDER(u.feps_e.p);
-  KH_LAUNDER(u.femit_b.p); KH_LAUNDER(u.femit_e.p); KH_LAUNDER(u.cost_offset.p);
-  KH_LAUNDER(u.must_links.p); KH_LAUNDER(u.must_toks.p);
-  KH_LAUNDER(u.tmp_slot.p); KH_LAUNDER(u.tmp_dirty.p); KH_LAUNDER(u.tmp_work0.p); KH_LAUNDER(u.tmp_work1.p);
-  KH_LAUNDER(u.tmp_epslist.p); KH_LAUNDER(u.tmp_f0.p); KH_LAUNDER(u.tmp_acc0.p); KH_LAUNDER(u.tmp_acc1.p); KH_LAUNDER(u.tmp_remap.p);
-  KH_LAUNDER(u.tok_frame_cap); KH_LAUNDER(u.link_frame_cap); KH_LAUNDER(u.window_cap);
-  KH_LAUNDER(u.surv_tok.p); KH_LAUNDER(u.surv_link.p); KH_LAUNDER(u.surv_tok_cap); KH_LAUNDER(u.surv_link_cap);
-  KH_LAUNDER(u.hash.p); KH_LAUNDER(u.hash_mask);
+  LaunderOne(u.ll); LaunderOne(u.ll_stride); LaunderOne(u.T); LaunderOne(u.tok_cap);
+  LaunderOne(u.tok_state.p); LaunderOne(u.tok_cost.p); LaunderOne(u.tok_extra.p);
+  LaunderOne(u.link_cap);
+  LaunderOne(u.link_dst.p); LaunderOne(u.link_arc.p); LaunderOne(u.link_src.p); LaunderOne(u.link_k.p); LaunderOne(u.link_a.p);
+  LaunderOne(u.frame_b.p); LaunderOne(u.frame_e.p); LaunderOne(u.feps_b.p); LaunderOne(u.feps_e.p);
+  LaunderOne(u.femit_b.p); LaunderOne(u.femit_e.p); LaunderOne(u.cost_offset.p);
+  LaunderOne(u.must_links.p); LaunderOne(u.must_toks.p);
+  LaunderOne(u.tmp_slot.p); LaunderOne(u.tmp_dirty.p); LaunderOne(u.tmp_work0.p); LaunderOne(u.tmp_work1.p);
+  LaunderOne(u.tmp_epslist.p); LaunderOne(u.tmp_f0.p); LaunderOne(u.tmp_acc0.p); LaunderOne(u.tmp_acc1.p); LaunderOne(u.tmp_remap.p);
+  LaunderOne(u.tok_frame_cap); LaunderOne(u.link_frame_cap); LaunderOne(u.window_cap);
+  LaunderOne(u.surv_tok.p); LaunderOne(u.surv_link.p); LaunderOne(u.surv_tok_cap); LaunderOne(u.surv_link_cap);
+  LaunderOne(u.hash.p); LaunderOne(u.hash_mask);
 }
 __device__ __forceinline__ void Launder(Params &p) {
-  KH_LAUNDER(p.rec.p); KH_LAUNDER(p.n_arcs.p); KH_LAUNDER(p.unit_ilabel.p);
-  KH_LAUNDER(p.start); KH_LAUNDER(p.num_units); KH_LAUNDER(p.num_eps); KH_LAUNDER(p.start_has_eps); KH_LAUNDER(p.ll_cols);
-  KH_LAUNDER(p.keep_ac); KH_LAUNDER(p.max_tid); KH_LAUNDER(p.lazy_prune); KH_LAUNDER(p.exact_order); KH_LAUNDER(p.cl_max_load);
-  KH_LAUNDER(p.hash_ratio); KH_LAUNDER(p.beam); KH_LAUNDER(p.lattice_beam); KH_LAUNDER(p.beam_delta); KH_LAUNDER(p.prune_scale);
-  KH_LAUNDER(p.max_active); KH_LAUNDER(p.min_active); KH_LAUNDER(p.prune_interval);
+  LaunderOne(p.rec.p); LaunderOne(p.n_arcs.p); LaunderOne(p.unit_ilabel.p);
+  LaunderOne(p.start); LaunderOne(p.num_units); LaunderOne(p.num_eps); LaunderOne(p.start_has_eps); LaunderOne(p.ll_cols);
+  LaunderOne(p.keep_ac); LaunderOne(p.max_tid); LaunderOne(p.lazy_prune); LaunderOne(p.exact_order); LaunderOne(p.cl_max_load);
+  LaunderOne(p.hash_ratio); LaunderOne(p.beam); LaunderOne(p.lattice_beam); LaunderOne(p.beam_delta); LaunderOne(p.prune_scale);
+  LaunderOne(p.max_active); LaunderOne(p.min_active); LaunderOne(p.prune_interval);
 }
 
 // Workgroup barrier that also waits for this wave's outstanding vector-memory
@@ -355,8 +330,7 @@ __device__ __forceinline__ void Stamp(const Utt &u, Blk &sh, int ph) {
 // row_bcast:31 across them - the gfx9 wave scan): six VALU instructions and nothing on the LDS pipe.  A __shfl_up step is
 // a ds_bpermute_b32 (an LDS-pipe instruction with its round trip) + the lane address + a select under a lane mask that
 // the compiler keeps in a scalar register pair - and, this kernel being short of scalar registers, reloads from a spill
-// VGPR with two v_readlane in front of every step.  KH_NO_DPP keeps the shuffles (same-box A/B).
-#ifndef KH_NO_DPP
+// VGPR with two v_readlane in front of every step.
 template <int kCtrl, int kRowMask>
 __device__ __forceinline__ int DppMov(int identity, int v) {
   return __builtin_amdgcn_update_dpp(identity, v, kCtrl, kRowMask, 0xf, false);
@@ -368,52 +342,27 @@ __device__ __forceinline__ int DppMov(int identity, int v) {
   v = OP(v, DppMov<0x118, 0xf>(id, v));         \
   v = OP(v, DppMov<0x142, 0xa>(id, v));         \
   v = OP(v, DppMov<0x143, 0xc>(id, v))
-#endif
 __device__ __forceinline__ int OpAddI(int a, int b) { return a + b; }
 __device__ __forceinline__ int OpMaxI(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int OpMinUBits(int a, int b) { return static_cast<uint32_t>(b) < static_cast<uint32_t>(a) ? b : a; }
 __device__ __forceinline__ int OpMinFBits(int a, int b) { return __float_as_int(fminf(__int_as_float(a), __int_as_float(b))); }
 // inclusive scans over the 64 lanes
 __device__ __forceinline__ int WaveIncSum(int v) {
-#ifndef KH_NO_DPP
   KH_DPP_SCAN(v, 0, OpAddI);
-#else
-  const int lane = KH_TIDX & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(v, o, 64); if (lane >= o) v += n; }
-#endif
   return v;
 }
 __device__ __forceinline__ int WaveIncMax(int v) {   // (values >= 0)
-#ifndef KH_NO_DPP
   KH_DPP_SCAN(v, 0, OpMaxI);
-#else
-  const int lane = KH_TIDX & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(v, o, 64); if (lane >= o) v = OpMaxI(v, n); }
-#endif
   return v;
 }
 __device__ __forceinline__ uint32_t WaveIncMinU(uint32_t u) {
   int v = static_cast<int>(u);
-#ifndef KH_NO_DPP
   KH_DPP_SCAN(v, -1, OpMinUBits);
-#else
-  const int lane = KH_TIDX & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(v, o, 64); if (lane >= o) v = OpMinUBits(v, n); }
-#endif
   return static_cast<uint32_t>(v);
 }
 __device__ __forceinline__ float WaveIncMinF(float f) {
   int v = __float_as_int(f);
-#ifndef KH_NO_DPP
   KH_DPP_SCAN(v, 0x7f800000, OpMinFBits);
-#else
-  const int lane = KH_TIDX & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(v, o, 64); if (lane >= o) v = OpMinFBits(v, n); }
-#endif
   return __int_as_float(v);
 }
 // the value of lane 63 (the total of an inclusive scan), in a scalar register
@@ -421,47 +370,34 @@ __device__ __forceinline__ int WaveLast(int v) { return __builtin_amdgcn_readlan
 // value of lane `src` (0 .. 63), per lane: ds_bpermute_b32 directly (__shfl also folds the caller's lane into the
 // source index, which costs two more VALU instructions and a live register per call site in a 64-lane wave)
 __device__ __forceinline__ int ShflI(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
-__device__ __forceinline__ uint32_t ShflU(uint32_t v, int src) { return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src << 2, static_cast<int>(v))); }
 __device__ __forceinline__ float ShflF(float v, int src) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v))); }
 __device__ __forceinline__ float WaveMinF(float f) { return __int_as_float(WaveLast(__float_as_int(WaveIncMinF(f)))); }
 // 64-bit reductions: the two halves travel separately (identity per half), the total ends in lane 63
-#ifndef KH_NO_DPP
 template <int kCtrl, int kRowMask>
 __device__ __forceinline__ unsigned long long DppMov64(int id_half, unsigned long long v) {
   const uint32_t hi = static_cast<uint32_t>(DppMov<kCtrl, kRowMask>(id_half, static_cast<int>(static_cast<uint32_t>(v >> 32))));
   const uint32_t lo = static_cast<uint32_t>(DppMov<kCtrl, kRowMask>(id_half, static_cast<int>(static_cast<uint32_t>(v))));
   return (static_cast<unsigned long long>(hi) << 32) | lo;
 }
-#endif
 __device__ __forceinline__ unsigned long long OpMinU64(unsigned long long a, unsigned long long b) { return b < a ? b : a; }
 __device__ __forceinline__ unsigned long long OpAddU64(unsigned long long a, unsigned long long b) { return a + b; }
 __device__ __forceinline__ unsigned long long WaveMinU64ToLast(unsigned long long v) {
-#ifndef KH_NO_DPP
   v = OpMinU64(v, DppMov64<0x111, 0xf>(-1, v));
   v = OpMinU64(v, DppMov64<0x112, 0xf>(-1, v));
   v = OpMinU64(v, DppMov64<0x114, 0xf>(-1, v));
   v = OpMinU64(v, DppMov64<0x118, 0xf>(-1, v));
   v = OpMinU64(v, DppMov64<0x142, 0xa>(-1, v));
   v = OpMinU64(v, DppMov64<0x143, 0xc>(-1, v));
-#else
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const unsigned long long n = __shfl_xor(v, o, 64); v = n < v ? n : v; }
-#endif
   return v;
 }
 __device__ __forceinline__ long long WaveSumLLToLast(long long x) {
   unsigned long long v = static_cast<unsigned long long>(x);
-#ifndef KH_NO_DPP
   v = OpAddU64(v, DppMov64<0x111, 0xf>(0, v));
   v = OpAddU64(v, DppMov64<0x112, 0xf>(0, v));
   v = OpAddU64(v, DppMov64<0x114, 0xf>(0, v));
   v = OpAddU64(v, DppMov64<0x118, 0xf>(0, v));
   v = OpAddU64(v, DppMov64<0x142, 0xa>(0, v));
   v = OpAddU64(v, DppMov64<0x143, 0xc>(0, v));
-#else
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-#endif
   return static_cast<long long>(v);
 }
 
@@ -780,7 +716,6 @@ __device__ __forceinline__ int LanePrefixCount(unsigned long long mask) {
 // save / branch, and on top of that the compiler's atomic optimizer wraps the single-lane atomic in its own
 // mbcnt / bcnt / multiply sequence - a dozen instructions per 64-arc batch.  Precondition: lane 0 is active.
 __device__ __forceinline__ int WaveLdsFetchAdd(__attribute__((address_space(3))) int *addr, int v) {
-#ifndef KH_NO_ASM_ATOMIC
   int r;
   unsigned long long saved;
   asm volatile(
@@ -793,11 +728,6 @@ __device__ __forceinline__ int WaveLdsFetchAdd(__attribute__((address_space(3)))
       : "v"(addr), "v"(v)
       : "memory");
   return __builtin_amdgcn_readfirstlane(r);
-#else
-  int r = 0;
-  if ((KH_TIDX & 63) == 0) r = __hip_atomic_fetch_add(addr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  return __builtin_amdgcn_readfirstlane(r);
-#endif
 }
 
 // Arc slot -> owning token inside a wave, for the independent-wave sweeps below.  A wave holds 64 tokens with their arc
@@ -862,21 +792,18 @@ __device__ __forceinline__ int ExpandWavesFiltered(const Utt &u, Arr<const KhInt
     sh->work_cursor = b;
     sh->bound_enc = Enc(*bound);
   }
-#ifndef KH_OWNER_SEARCH
   OwnerScan os = OwnerScanInit(sh);
-#endif
   Arr<uint32_t> w_cost = u.tok_cost;
   Arr<int32_t> w_state = u.tok_state;
-  KH_LAUNDER(w_cost.p); KH_LAUNDER(w_state.p);
+  LaunderOne(w_cost.p); LaunderOne(w_state.p);
   KhSync();
   uint32_t my_bound_enc = Enc(*bound);
-#ifndef KH_NO_CLAIM_PREFETCH
   // A wave always holds its NEXT claim: cursor and the 64 tokens' cost / state are requested while the current claim's
   // batches run, so a claim starts with the record headers instead of two dependent round trips (554.5 against 557 ms;
-  // no change of the kernel's scratch).  KH_CLAIM_PREFETCH2: the next claim's record headers as well (its arc counts),
-  // requested from the cost / state that arrived during the claim before - two claims deep.  Measured 559-569 ms
-  // against 553: a wave that owns three claims at a time (48 of a frame's ~76 taken up front) balances worse than
-  // the round trip is worth; off by default.
+  // no change of the kernel's scratch).  Two claims deep - the next claim's record headers (its arc counts) as well,
+  // requested from the cost / state that arrived during the claim before - was measured and not kept: 559-569 ms
+  // against 553, a wave that owns three claims at a time (48 of a frame's ~76 taken up front) balances worse than
+  // the round trip is worth (NOTEBOOK.md §12).
   int base_next = WaveLdsFetchAdd(&sh->work_cursor, 64);
   uint32_t co_next = 0u;
   int st_next = 0;
@@ -885,38 +812,7 @@ __device__ __forceinline__ int ExpandWavesFiltered(const Utt &u, Arr<const KhInt
     co_next = LoadCostEnc(&w_cost[ic]);
     st_next = w_state[ic];
   }
-#ifdef KH_CLAIM_PREFETCH2
-  int base_nn = WaveLdsFetchAdd(&sh->work_cursor, 64);
-  uint32_t co_nn = 0u;
-  int st_nn = 0, cnt_next = 0;
-  if (base_nn < e) {
-    const int ic = min(base_nn + lane, e - 1);
-    co_nn = LoadCostEnc(&w_cost[ic]);
-    st_nn = w_state[ic];
-  }
-  if (base_next < e && base_next + lane < e && Dec(co_next) <= cutoff) cnt_next = rec[st_next].x;
-#endif
-#endif
   for (;;) {
-#if !defined(KH_NO_CLAIM_PREFETCH) && defined(KH_CLAIM_PREFETCH2)
-    const int base = base_next;
-    if (base >= e) break;
-    const int i = base + lane;
-    const bool in_range = i < e;
-    const uint32_t co = co_next;
-    int st = st_next;
-    const int cnt_pre = cnt_next;
-    // shift the pipeline: claim + 1 becomes the next one (its headers are requested now), a new claim + 2 is taken
-    base_next = base_nn; co_next = co_nn; st_next = st_nn;
-    cnt_next = 0;
-    if (base_next < e && base_next + lane < e && Dec(co_next) <= cutoff) cnt_next = rec[st_next].x;
-    base_nn = WaveLdsFetchAdd(&sh->work_cursor, 64);
-    if (base_nn < e) {
-      const int icn = min(base_nn + lane, e - 1);
-      co_nn = LoadCostEnc(&w_cost[icn]);
-      st_nn = w_state[icn];
-    }
-#elif !defined(KH_NO_CLAIM_PREFETCH)
     const int base = base_next;
     if (base >= e) break;
     const int i = base + lane;
@@ -929,25 +825,12 @@ __device__ __forceinline__ int ExpandWavesFiltered(const Utt &u, Arr<const KhInt
       co_next = LoadCostEnc(&w_cost[icn]);
       st_next = w_state[icn];
     }
-#else
-    const int base = WaveLdsFetchAdd(&sh->work_cursor, 64);
-    if (base >= e) break;
-    const int i = base + lane;
-    const bool in_range = i < e;
-    const int ic = min(i, e - 1);
-    const uint32_t co = LoadCostEnc(&w_cost[ic]);
-    int st = w_state[ic];
-#endif
     KH_BOUND(1, st, 0, 0x7ffffff0);
     const bool need = in_range && Dec(co) <= cutoff;
     int ab = 0, cnt = 0;
     if (need) {  // the emitting arcs follow the state's header in its record
       ab = st + 1;
-#if !defined(KH_NO_CLAIM_PREFETCH) && defined(KH_CLAIM_PREFETCH2)
-      cnt = cnt_pre;
-#else
       cnt = rec[st].x;
-#endif
     }
     const int inc = WaveIncSum(cnt);
     const int loff = inc - cnt;
@@ -958,32 +841,17 @@ __device__ __forceinline__ int ExpandWavesFiltered(const Utt &u, Arr<const KhInt
       *bound = fminf(*bound, Dec(be));
       my_bound_enc = min(my_bound_enc, be);
     }
-#ifndef KH_OWNER_SEARCH
     os.carry = -1;
     const int rel = ab - loff;   // arc index = rel(owner) + slot
-#endif
     for (int q0 = 0; q0 < total; q0 += 64) {  // uniform over the wave
       const int q = q0 + lane;
       const bool valid = q < total;
       // owner = the LAST token whose first slot is <= q (tokens without arcs share their
       // successor's first slot and are skipped by "last")
-#ifndef KH_OWNER_SEARCH
       const int lo = OwnerLane(os, cnt, loff, q0, lane);
       const int o_rel = ShflI(rel, lo);
       const float o_co = ShflF(cof, lo);
       const int o_ai = o_rel + q;
-#else
-      int lo = 0, hi = 63;
-#pragma unroll
-      for (int step = 0; step < 6; step++) {
-        const int mid = (lo + hi + 1) >> 1;
-        const int v = __shfl(loff, mid, 64);
-        if (v <= q) lo = mid; else hi = mid - 1;
-      }
-      const int o_off = __shfl(loff, lo, 64), o_ab = __shfl(ab, lo, 64);
-      const float o_co = __shfl(cof, lo, 64);
-      const int o_ai = o_ab + (q - o_off);
-#endif
       bool keep = false;
       if (valid) {
         load(0, base + lo, o_co, o_ai);
@@ -1028,7 +896,7 @@ __device__ Cutoff GetCutoff(const Utt &u, const Params &p, int b, int e, Blk &sh
   Cutoff c;
   Arr<uint32_t> g_cost = u.tok_cost;
   Arr<int32_t> g_state = u.tok_state;
-  KH_LAUNDER_GC(g_cost.p); KH_LAUNDER_GC(g_state.p);
+  LaunderOne(g_cost.p); LaunderOne(g_state.p);
   const int n = e - b;
   c.count = n;
   unsigned long long best = ~0ull;
@@ -1353,7 +1221,6 @@ __device__ int ClosureLds(const Utt &u, const Params &p, int frame, float cutoff
       u.link_k[l] = k;
     }
   }
-#ifndef KH_CL_BLOCKSUM
   {  // the arcs visited, for the utterance's counter: one LDS add per wave (no barrier of its own)
     const long long wave_arcs = WaveSumLLToLast(my_arcs);
     if ((KH_TIDX & 63) == 63 && wave_arcs != 0)
@@ -1366,17 +1233,6 @@ __device__ int ClosureLds(const Utt &u, const Params &p, int frame, float cutoff
     u.feps_b[frame] = blk_b;
     u.feps_e[frame] = sh->link_end;
   }
-#else
-  KhSync();
-  if (Uni(sh->status) != 0) return -1;
-  const long long tot_arcs = BlockSumLL(my_arcs, sh);
-  if (KH_TIDX == 0) {
-    sh->link_end = sh->link_cursor;
-    sh->arcs_expanded += tot_arcs;
-    u.feps_b[frame] = blk_b;
-    u.feps_e[frame] = sh->link_end;
-  }
-#endif
   KhSync();
   Stamp(u, sh, 4);
   return 1;
@@ -1418,18 +1274,16 @@ __device__ bool ProcessNonemitting(const Utt &u_in, const Params &p_in, int fram
   // the phase's own copies of the pointers it uses (see ProcessEmitting: kept in scalar registers for its duration)
   Utt u = u_in;
   Params p = p_in;
-  KH_LAUNDER_NE(u.tmp_epslist.p); KH_LAUNDER_NE(u.tmp_work0.p); KH_LAUNDER_NE(u.tmp_work1.p); KH_LAUNDER_NE(u.tmp_dirty.p);
-  KH_LAUNDER_NE(u.tok_cost.p); KH_LAUNDER_NE(u.tok_state.p); KH_LAUNDER_NE(u.tok_extra.p); KH_LAUNDER_NE(u.tmp_slot.p);
-  KH_LAUNDER_NE(u.hash.p); KH_LAUNDER_NE(u.hash_mask);
-  KH_LAUNDER_NE(u.link_dst.p); KH_LAUNDER_NE(u.link_src.p); KH_LAUNDER_NE(u.link_arc.p); KH_LAUNDER_NE(u.link_k.p);
-  KH_LAUNDER_NE(p.rec.p); KH_LAUNDER_NE(p.n_arcs.p);
-  KH_LAUNDER_NE(u.feps_b.p); KH_LAUNDER_NE(u.feps_e.p); KH_LAUNDER_NE(u.tmp_f0.p);
+  LaunderOne(u.tmp_epslist.p); LaunderOne(u.tmp_work0.p); LaunderOne(u.tmp_work1.p); LaunderOne(u.tmp_dirty.p);
+  LaunderOne(u.tok_cost.p); LaunderOne(u.tok_state.p); LaunderOne(u.tok_extra.p); LaunderOne(u.tmp_slot.p);
+  LaunderOne(u.hash.p); LaunderOne(u.hash_mask);
+  LaunderOne(u.link_dst.p); LaunderOne(u.link_src.p); LaunderOne(u.link_arc.p); LaunderOne(u.link_k.p);
+  LaunderOne(p.rec.p); LaunderOne(p.n_arcs.p);
+  LaunderOne(u.feps_b.p); LaunderOne(u.feps_e.p); LaunderOne(u.tmp_f0.p);
   if (from_list) {   // (false: frame 0, whose start token DecodeInit entered in the global hash itself)
-#ifndef KH_NO_LDS_CLOSURE
     const int rc = ClosureLds(u, p, frame, cutoff, sh);
     if (u.phase_cycles != nullptr && KH_TIDX == 0) sh->phase[rc != 0 ? 38 : 39] += 1;
     if (rc != 0) return rc > 0;
-#endif
     ClosureGeneralPrep(u, sh);
   }
   const int fb = Uni(sh->front_b);
@@ -1616,9 +1470,9 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
   Arr<uint32_t> e_cost = u.tok_cost;
   Arr<float> e_f0 = u.tmp_f0;
   if constexpr (kLocal) {
-    KH_LAUNDER_P2(e_f0.p);
-    KH_LAUNDER_P2(e_k.p); KH_LAUNDER_P2(e_extra.p); KH_LAUNDER_P2(e_dst.p); KH_LAUNDER_P2(e_state.p); KH_LAUNDER_P2(e_epslist.p);
-    KH_LAUNDER_P2(e_work0.p); KH_LAUNDER_P2(e_work1.p); KH_LAUNDER_P2(e_cost.p);
+    LaunderOne(e_f0.p);
+    LaunderOne(e_k.p); LaunderOne(e_extra.p); LaunderOne(e_dst.p); LaunderOne(e_state.p); LaunderOne(e_epslist.p);
+    LaunderOne(e_work0.p); LaunderOne(e_work1.p); LaunderOne(e_cost.p);
   }
   auto keys = LdsKeys(sh);
   auto vals = LdsVals(sh);
@@ -1629,18 +1483,8 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
   // in slot order — so the tokens of neighbouring states are neighbours in the next frame's
   // expansion: their arc-offset words share a cache line and their arcs are contiguous in the
   // arc table (an HCLG numbers the states of an HMM chain / a lexicon-tree branch consecutively).
-#ifndef KH_PART_CAND
-#define KH_PART_CAND 11000   // accepted candidates per part of pass 2 (7 k / 9 k / 13 k / 15 k measured: +6 % / 0 / +1 % / +8 %)
-#endif
-#ifndef KH_LOC_BITS
-#define KH_LOC_BITS 5
-#endif
   // A state id is the unit index of its record (header + emitting arcs: ~3 units for the states of
   // an HMM chain), so a block of 2^kLocBits table slots stands for 2^(kLocBits + kLocShift) units.
-#ifndef KH_LOC_SHIFT
-#define KH_LOC_SHIFT 1
-#endif
-  constexpr int kLocBits = KH_LOC_BITS, kLocShift = KH_LOC_SHIFT;
   auto lds_slot = [](uint32_t h, int32_t ns) {
     return ((h << kLocBits) | ((static_cast<uint32_t>(ns) >> kLocShift) & ((1u << kLocBits) - 1u))) & (kLdsSlots - 1);
   };
@@ -1649,8 +1493,8 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
   // parts (the parts nest, and resolved links are marked, so nothing is done twice)
   int parts = 1;
   if constexpr (kLocal) {   // (reference order: the caller has counted the live candidates)
-    while (parts * KH_PART_CAND < n_acc_known) parts *= 2;
-  } else if (link_frame_e - link_frame_b > KH_PART_CAND) {
+    while (parts * kPartCand < n_acc_known) parts *= 2;
+  } else if (link_frame_e - link_frame_b > kPartCand) {
     int n_acc_mine = 0;
     {
       constexpr int kCU = 8;   // loads of a lane in flight together (a frame of this size took 11+ dependent round trips here)
@@ -1663,7 +1507,7 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
       }
     }
     const int n_acc = static_cast<int>(BlockSumLL(n_acc_mine, sh));
-    while (parts * KH_PART_CAND < n_acc) parts *= 2;
+    while (parts * kPartCand < n_acc) parts *= 2;
     if (u.phase_cycles != nullptr && KH_TIDX == 0) sh->phase[32] += n_acc;
   }
   if (u.phase_cycles != nullptr && KH_TIDX == 0) { sh->phase[31] += link_frame_e - link_frame_b; sh->phase[13] += 0; }
@@ -1685,13 +1529,8 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
         tc[0] = 0.0f; tc[1] = 0.0f; tc[2] = 0.0f; tc[3] = 0.0f;
         nsv[0] = n4.x; nsv[1] = n4.y; nsv[2] = n4.z; nsv[3] = n4.w;
       } else if (base + kMU <= link_frame_e) {
-#ifndef KH_NO_NT
         const KhFloat4 t4 = last_read ? Load4F_NT(e_k, base) : Load4F(e_k, base);
         const KhInt4 n4 = last_read ? Load4I_NT(e_dst, base) : Load4I(e_dst, base);
-#else
-        const KhFloat4 t4 = Load4F(e_k, base);
-        const KhInt4 n4 = Load4I(e_dst, base);
-#endif
         tc[0] = t4.x; tc[1] = t4.y; tc[2] = t4.z; tc[3] = t4.w;
         nsv[0] = n4.x; nsv[1] = n4.y; nsv[2] = n4.z; nsv[3] = n4.w;
       } else {
@@ -1705,24 +1544,18 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
         }
       }
     };
-    // KH_P2_PREFETCH: the NEXT group's loads issued before this group's candidates are inserted (the sweep waits for a
-    // round trip per trip: loads, s_waitcnt, work - ten in a row per part for a 40 k-candidate frame, twice per part).
-    // Measured: 575-581 ms against 558 without - the eight registers of the group in flight push the kernel's scratch
-    // from 144 to 164 bytes per lane, which costs more than the round trips; off by default.
-    float tc[kMU], tc_next[kMU];
-    int32_t nsv[kMU], nsv_next[kMU];
+    // The sweeps of (B) and (D) wait for a round trip per trip: loads, s_waitcnt, work - ten in a row per part for a
+    // 40 k-candidate frame, twice per part.  Issuing the NEXT group's loads before this group's candidates are inserted
+    // was measured and not kept: 575-581 ms against 558 - the eight registers of the group in flight push the kernel's
+    // scratch from 144 to 164 bytes per lane, which costs more than the round trips (NOTEBOOK.md §12).
+    float tc[kMU];
+    int32_t nsv[kMU];
     {
       const int base0 = link_frame_b + KH_TIDX * kMU;
       if (base0 < link_frame_e) load_group(base0, tc, nsv);
     }
     for (int base = link_frame_b + KH_TIDX * kMU; base < link_frame_e; base += NT * kMU) {
-#ifdef KH_P2_PREFETCH
-      const bool more = base + NT * kMU < link_frame_e;
-#else
-      const bool more = false;
       if (base != link_frame_b + static_cast<int>(KH_TIDX) * kMU) load_group(base, tc, nsv);
-#endif
-      if (more) load_group(base + NT * kMU, tc_next, nsv_next);
 #pragma unroll
       for (int j = 0; j < kMU; j++) {
         const float tot_cost = tc[j];
@@ -1752,10 +1585,6 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
         }
         if (probes == 256) { sh->flag = 1; continue; }  // the table is (nearly) full
         (void)__hip_atomic_fetch_min(&vals[slot], Enc(tot_cost), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      if (more) {
-#pragma unroll
-        for (int j = 0; j < kMU; j++) { tc[j] = tc_next[j]; nsv[j] = nsv_next[j]; }
       }
     }
     KhSync();
@@ -1791,11 +1620,7 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
       e_state[idx] = ns & kStateMask;
       const uint32_t cost_enc = vals[i];
       e_cost[idx] = cost_enc;
-#ifndef KH_NO_NT
       __builtin_nontemporal_store(0.0f, &e_extra[idx]);  // "tokens on the currently final frame have zero extra_cost" :241
-#else
-      e_extra[idx] = 0.0f;  // "tokens on the currently final frame have zero extra_cost" :241
-#endif
       if (kLocal && fuse_ord) vals[i] = (0x7FFFFu << 13) | static_cast<uint32_t>(off[j]);
       else vals[i] = static_cast<uint32_t>(idx);
       // these tokens are the closure's first work list (every one has a finite cost)
@@ -1828,13 +1653,7 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
     }
     for (int base = link_frame_b + KH_TIDX * kMU; base < link_frame_e; base += NT * kMU) {
       const bool full = base + kMU <= link_frame_e;
-#ifdef KH_P2_PREFETCH
-      const bool more = base + NT * kMU < link_frame_e;
-#else
-      const bool more = false;
       if (base != link_frame_b + static_cast<int>(KH_TIDX) * kMU) load_group(base, tc, nsv);
-#endif
-      if (more) load_group(base + NT * kMU, tc_next, nsv_next);   // (as in (B): the next group's loads under this group's work)
       // reference order: the group's ordinals and state ids requested WITH its costs and destinations (one 16-byte load
       // per array) - read where they are used, inside the loop below, each was a dependent round trip behind the stores of
       // the candidate before it (the compiler cannot move a load over a store that may alias): round 6's fine stamps
@@ -1890,15 +1709,7 @@ __device__ __forceinline__ bool EmitPass2(const Utt &u, Blk &sh, int nb, int tok
       if (full && wrote) {   // the lane owns the four slots: one 16-byte store
         KhInt4 o4;
         o4.x = nsv[0]; o4.y = nsv[1]; o4.z = nsv[2]; o4.w = nsv[3];
-#ifndef KH_NO_NT
         if (k + 1 == parts) Store4I_NT(e_dst, base, o4); else Store4I(e_dst, base, o4);   // (the last part: nobody reads the links before pruning)
-#else
-        Store4I(e_dst, base, o4);
-#endif
-      }
-      if (more) {
-#pragma unroll
-        for (int j = 0; j < kMU; j++) { tc[j] = tc_next[j]; nsv[j] = nsv_next[j]; }
       }
     }
     KhSync();
@@ -1925,11 +1736,7 @@ __device__ __forceinline__ void StageScoreRow(const Utt &u, const Params &p, Blk
   for (int c0 = KH_TIDX; c0 < p.ll_cols; c0 += NT * kU) {
     float v[kU];
 #pragma unroll
-#ifndef KH_NO_NT
     for (int k = 0; k < kU; k++) v[k] = c0 + k * NT < p.ll_cols ? __builtin_nontemporal_load(&src[c0 + k * NT]) : 0.0f;
-#else
-    for (int k = 0; k < kU; k++) v[k] = c0 + k * NT < p.ll_cols ? src[c0 + k * NT] : 0.0f;
-#endif
 #pragma unroll
     for (int k = 0; k < kU; k++)
       if (c0 + k * NT < p.ll_cols) sh.ll_row[c0 + k * NT] = v[k];
@@ -2007,8 +1814,8 @@ __device__ bool ProcessEmitting(const Utt &u, const Params &p, int frame, int b,
   Arr<float> x_k = u.link_k, x_a = u.link_a;
   GP(const float) x_ll = u.ll + static_cast<size_t>(frame) * u.ll_stride;
   int x_keep_ac = p.keep_ac, x_ll_cols = p.ll_cols;
-  KH_LAUNDER(x_rec.p); KH_LAUNDER(x_dst.p); KH_LAUNDER(x_src.p); KH_LAUNDER(x_arc.p); KH_LAUNDER(x_k.p); KH_LAUNDER(x_a.p);
-  KH_LAUNDER(x_ll); KH_LAUNDER(x_keep_ac); KH_LAUNDER(x_ll_cols);
+  LaunderOne(x_rec.p); LaunderOne(x_dst.p); LaunderOne(x_src.p); LaunderOne(x_arc.p); LaunderOne(x_k.p); LaunderOne(x_a.p);
+  LaunderOne(x_ll); LaunderOne(x_keep_ac); LaunderOne(x_ll_cols);
   const int link_frame_e = ExpandWavesFiltered(
       u, x_rec, b, e, c.cur_cutoff, link_frame_b, u.link_frame_cap, &my_arcs, sh, &est, &bound,
       [&](int k, int src, float src_cost, int ai) {
@@ -2030,18 +1837,12 @@ __device__ bool ProcessEmitting(const Utt &u, const Params &p, int frame, int b,
       },
       [&](int k, int l) {
         x_dst[l] = -2 - c_arc[k].w;  // <= -2: the HCLG next state (+ flags), unresolved; token index after pass 2
-#ifndef KH_NO_NT
         // (source, arc and acoustic cost of a link are not read again before the next pruning visit: non-temporal stores -
         // same-box A/B 546 -> 535 ms, with the other nt accesses of the file 531: the lines they no longer displace in L2
         // are arc records the next frames re-read)
         __builtin_nontemporal_store(c_src[k], &x_src[l]);
         __builtin_nontemporal_store(c_ai[k], &x_arc[l]);
         if (x_keep_ac) __builtin_nontemporal_store(c_ac[k], &x_a[l]);
-#else
-        x_src[l] = c_src[k];
-        x_arc[l] = c_ai[k];
-        if (x_keep_ac) x_a[l] = c_ac[k];
-#endif
         x_k[l] = c_tot[k];
       });
   if (link_frame_e < 0) return false;
@@ -2107,12 +1908,7 @@ __device__ __forceinline__ void BlockExScanSumMin(int v, uint32_t m, int *ex_sum
     sh->wsum[b1][w] = inc;
     sh->wred[b2][w] = im;
   }
-#ifndef KH_NO_DPP
   const uint32_t pm = static_cast<uint32_t>(DppMov<0x138, 0xf>(-1, static_cast<int>(im)));   // wave_shr:1; lane 0 keeps the identity
-#else
-  uint32_t pm = static_cast<uint32_t>(__shfl_up(static_cast<int>(im), 1, 64));
-  if (lane == 0) pm = 0xFFFFFFFFu;
-#endif
   KhSync();
   int before = 0, all = 0;
   uint32_t bm = 0xFFFFFFFFu, am = 0xFFFFFFFFu;
@@ -2677,7 +2473,6 @@ __device__ __forceinline__ int LdsExScanInPlace(LdsU32 a, int W, Blk &sh) {
   }
   return total;
 }
-__device__ __forceinline__ uint32_t LdsLoadU(LdsU32 p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ int BitRank(LdsU32 bits, LdsU32 pre, uint32_t q) {   // set bits below bit q
   return static_cast<int>(pre[q >> 5]) + __popc(bits[q >> 5] & ((1u << (q & 31u)) - 1u));
 }
@@ -3063,7 +2858,6 @@ __device__ int OrderFrontierFast(const Utt &u, const Params &p, int nb, int fe, 
       // interpreter of the LIFO queue below.  ~33 insertions per frame took it ~50 us (round-5 stamps), one lane
       // chasing LDS round trips; this takes a few barriers.
       bool by_walks = false;
-#ifndef KH_X_NO_WALKS
       if (n_new < kRpNodes / 2 && eps_emit <= kRpNodes) {
         typedef __attribute__((address_space(3))) unsigned long long *LdsU64;
         // [n_new] over newq (written last); the area starts on a 4-byte boundary: the 64-bit atomics need 8
@@ -3129,7 +2923,6 @@ __device__ int OrderFrontierFast(const Utt &u, const Params &p, int nb, int fe, 
         if (u.phase_cycles != nullptr && tid == 0) sh->phase[by_walks ? 64 : 65] += 1;
         LdsSync();
       }
-#endif
       if (!by_walks && tid < 64) {
         const int cnt = ReplayClosureWave(l_ncost, l_nlr, l_dstack, l_newq, l_code, l_lw, UX(x_stack), eps_emit, cutoff, n_new, sh);
         if (tid == 0) sh->x_n_new = cnt;
@@ -3567,9 +3360,7 @@ __device__ bool OrderFrontier(const Utt &u, const Params &p, int nb, int fe, int
     sh->phase[n <= 8160 ? 61 : (n <= 16384 ? 62 : 63)] += 1;
   }
   int rc = 2;
-#ifndef KH_X_NO_LDS_TIER
   if (fast) rc = OrderFrontierLds(u, p, nb, fe, lb, le, cutoff, sh);
-#endif
   if (fast && rc == 2) rc = OrderFrontierFast(u, p, nb, fe, lb, le, cutoff, sh);
   if (u.phase_cycles != nullptr && KH_TIDX == 0) {
     const long long t1 = static_cast<long long>(__builtin_amdgcn_s_memtime());
@@ -3577,12 +3368,7 @@ __device__ bool OrderFrontier(const Utt &u, const Params &p, int nb, int fe, int
     t0 = t1;
   }
   if (rc == 2) {
-#ifdef KH_X_NO_SORT
-    if (KH_TIDX == 0) sh->status = 9;
-    rc = 0;
-#else
     rc = OrderFrontierSort(u, p, nb, fe, lb, le, cutoff, sh) ? 1 : 0;
-#endif
     if (u.phase_cycles != nullptr && KH_TIDX == 0) {
       sh->phase[60] += static_cast<long long>(__builtin_amdgcn_s_memtime()) - t0;
       sh->phase[57] += 1;
@@ -3657,10 +3443,10 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
   Arr<int32_t> x_dst = u.link_dst, x_src = u.link_src, x_arc = u.link_arc;
   Arr<float> x_k = u.link_k, x_a = u.link_a;
   int x_keep_ac = p.keep_ac;
-  KH_LAUNDER_X(x_rec.p); KH_LAUNDER_X(x_cost.p); KH_LAUNDER_X(x_state.p); KH_LAUNDER_X(x_ll); KH_LAUNDER_X(x_ll_cols);
-  KH_LAUNDER_X(xp_pos.p); KH_LAUNDER_X(xp_c.p); KH_LAUNDER_X(xp_m.p); KH_LAUNDER_X(xp_ord.p); KH_LAUNDER_X(xp_csid.p);
-  KH_LAUNDER_X(x_dst.p); KH_LAUNDER_X(x_src.p); KH_LAUNDER_X(x_arc.p); KH_LAUNDER_X(x_k.p); KH_LAUNDER_X(x_a.p);
-  KH_LAUNDER_X(x_keep_ac);
+  LaunderOne(x_rec.p); LaunderOne(x_cost.p); LaunderOne(x_state.p); LaunderOne(x_ll); LaunderOne(x_ll_cols);
+  LaunderOne(xp_pos.p); LaunderOne(xp_c.p); LaunderOne(xp_m.p); LaunderOne(xp_ord.p); LaunderOne(xp_csid.p);
+  LaunderOne(x_dst.p); LaunderOne(x_src.p); LaunderOne(x_arc.p); LaunderOne(x_k.p); LaunderOne(x_a.p);
+  LaunderOne(x_keep_ac);
   OwnerScan os = OwnerScanInit(sh);
   const float est0 = BlockMinF(est, sh);   // (its barrier publishes the cursors)
   XS(59);
@@ -3682,23 +3468,14 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
   // leaves the running cutoff as what it is - a step function with a handful of steps: the positions where it drops and
   // the values it drops to, as a short list in memory.  A candidate at or under the frame's FINAL cutoff is accepted
   // without looking (it is under every earlier value); the others - under one in a hundred - walk the list.
-#ifndef KH_X_NO_MID_TIER
   constexpr int kMidBits = 2 * kLdsSlots / 32, kMidBitBase = kLdsSlots - kMidBits;
   const bool mid_scan = !lds_scan && n <= 2 * kLdsSlots && x_ll_cols <= kMidBitBase && p.max_emit < 65536 && p.exact_order == 1;
-#else
-  constexpr int kMidBits = 0, kMidBitBase = 0;
-  const bool mid_scan = false;
-#endif
   // Round 6: in the two LDS tiers the sweep leaves every candidate's place in the walk as (list position of its source
   // token) << 16 | (index of the arc among the token's arcs) in x_ord; the acceptance sweep turns it into the ordinal with
   // the scan's results alone - it used to read the candidate's source and arc and GATHER the source's position and state
   // (two gathers per candidate), and the candidates' source / arc words, not read again before pruning, go out with
   // non-temporal stores as in the canonical sweep.
-#ifndef KH_X_NO_KEY_ORD
   const bool key_ord = (lds_scan || mid_scan) && p.max_emit < 65536;
-#else
-  const bool key_ord = false;
-#endif
   const LdsU32 sK = (LdsU32)LdsKeys(sh);
   const LdsU32 sV = (LdsU32)LdsVals(sh);
   if (lds_scan)
@@ -3713,18 +3490,9 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
   // inclusive minimum over the lanes that have the same owner (the lanes of a token are consecutive and `lo` is
   // non-decreasing): the wave scan with a segment test, on DPP
   auto seg_min_scan = [&](float m, int lo) -> float {
-#ifndef KH_NO_DPP
 #define KH_SEG_STEP(ctrl, rm) { const float nm = __int_as_float(DppMov<ctrl, rm>(0x7f800000, __float_as_int(m))); const int nlo = DppMov<ctrl, rm>(-2, lo); if (nlo == lo) m = fminf(m, nm); }
     KH_SEG_STEP(0x111, 0xf) KH_SEG_STEP(0x112, 0xf) KH_SEG_STEP(0x114, 0xf) KH_SEG_STEP(0x118, 0xf) KH_SEG_STEP(0x142, 0xa) KH_SEG_STEP(0x143, 0xc)
 #undef KH_SEG_STEP
-#else
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float nm = __shfl_up(m, o, 64);
-      const int nlo = __shfl_up(lo, o, 64);
-      if (lane >= o && nlo == lo) m = fminf(m, nm);
-    }
-#endif
     return m;
   };
   // ---- the sweep: candidates under min(bound of the token's run, the token's own earlier arcs); per token M and count.
@@ -3736,19 +3504,15 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
   int base_next = WaveLdsFetchAdd(&sh->work_cursor, 64);
   uint32_t co_next = 0u;
   int st_next = 0, pos_next = 0;
-  // (round 6, -DKH_X_CNT_PREFETCH: measured and NOT kept) hc_next: the emitting-arc count in the header of the next claim's
-  // states, requested while the current claim's batches are in flight - the count is the first of a claim's dependent round
-  // trips (state -> header -> arcs).  Same-box A/B 902 ms with it, 892 without: the extra register and the header reads of
-  // tokens above the cutoff cost more than the round trip they hide next to 31 other waves.
-  int hc_next = 0;
+  // (Round 6, measured and NOT kept: the emitting-arc count in the header of the next claim's states requested as well,
+  // while the current claim's batches are in flight - the count is the first of a claim's dependent round trips, state ->
+  // header -> arcs.  Same-box A/B 902 ms with it, 892 without: the extra register and the header reads of tokens above
+  // the cutoff cost more than the round trip they hide next to 31 other waves.)
   if (base_next < e) {
     const int icn = min(base_next + lane, e - 1);
     co_next = LoadCostEnc(&x_cost[icn]);
     st_next = x_state[icn];
     pos_next = xp_pos[icn - b];
-#ifdef KH_X_CNT_PREFETCH
-    hc_next = x_rec[st_next].x;
-#endif
   }
   for (;;) {
     const int base = base_next;
@@ -3758,7 +3522,6 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
     const uint32_t co = co_next;
     int st = st_next;
     const int pos = pos_next;
-    const int hc = hc_next;
     const int blk = pos >> bshift;
     base_next = WaveLdsFetchAdd(&sh->work_cursor, 64);
     if (base_next < e) {
@@ -3767,17 +3530,12 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
       st_next = x_state[icn];
       pos_next = xp_pos[icn - b];
     }
-    bool hc_asked = false;
     KH_BOUND(1, st, 0, 0x7ffffff0);
     const bool need = in_range && Dec(co) <= c.cur_cutoff;
     int ab = 0, cnt = 0;
     if (need) {
       ab = st + 1;
-#ifdef KH_X_CNT_PREFETCH
-      cnt = hc;
-#else
       cnt = x_rec[st].x;
-#endif
     }
     const float bnd = Dec(__hip_atomic_load(&sh->x_cb[blk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
     const int inc = WaveIncSum(cnt);
@@ -3813,15 +3571,9 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
         // some arc of the batch lowers the cutoff in front of the arcs behind it: the token's own earlier arcs count
         float m = (m0 == m0) ? m0 : inf;   // (a NaN never lowers it)
         m = seg_min_scan(m, lo);
-#ifndef KH_NO_DPP
         const float pm = __int_as_float(DppMov<0x138, 0xf>(0x7f800000, __float_as_int(m)));   // wave_shr:1
         const int plo = DppMov<0x138, 0xf>(-2, lo);
         const float before = plo == lo ? pm : inf;
-#else
-        const float pm = __shfl_up(m, 1, 64);
-        const int plo = __shfl_up(lo, 1, 64);
-        const float before = (lane >= 1 && plo == lo) ? pm : inf;
-#endif
         keep = keep && !(tot > before);
         const bool has = cnt > 0 && loff < q0 + 64 && loff + cnt > q0;
         const int tail = min(loff + cnt, q0 + 64) - 1 - q0;
@@ -3839,7 +3591,6 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
           if (keep) {
             const int l = at + LanePrefixCount(kb);
             x_dst[l] = -2 - arc.w;
-#ifndef KH_NO_NT
             if (key_ord) {
               __builtin_nontemporal_store(base + lo, &x_src[l]);
               __builtin_nontemporal_store(ai, &x_arc[l]);
@@ -3849,31 +3600,12 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
               x_arc[l] = ai;
             }
             if (x_keep_ac) __builtin_nontemporal_store(ac, &x_a[l]);   // (not read before the next pruning visit)
-#else
-            x_src[l] = base + lo;
-            x_arc[l] = ai;
-            if (key_ord) xp_ord[l - link_frame_b] = o_pk + q;
-            if (x_keep_ac) x_a[l] = ac;
-#endif
             x_k[l] = tot;
-#if !defined(KH_NO_NT) && !defined(KH_X_NO_NT_AUX)
             __builtin_nontemporal_store(arc.y, &xp_csid[l - link_frame_b]);   // the caller's id of the destination state (ArcPdfKernel); read once, by pass 2
-#else
-            xp_csid[l - link_frame_b] = arc.y;   // the caller's id of the destination state (ArcPdfKernel)
-#endif
           }
         }
       }
-#ifdef KH_X_CNT_PREFETCH
-      if (!hc_asked) {   // behind the claim's FIRST batch: the next claim's states have landed (they were asked for before this batch's arcs)
-        hc_asked = true;
-        if (base_next < e) hc_next = x_rec[st_next].x;
-      }
-#endif
     }
-#ifdef KH_X_CNT_PREFETCH
-    if (!hc_asked && base_next < e) hc_next = x_rec[st_next].x;   // (a claim without arcs)
-#endif
     if (in_range) {
       const uint32_t me = Enc(acc);   // (+inf for a token none of whose arcs came under the bound)
       if (lds_scan) {
@@ -3892,7 +3624,6 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
         xp_m[i - b] = me;
         xp_c[i - b] = cnt;
       }
-#ifndef KH_X_NO_RUN_BOUND
       if (me < kEncInf) {
 #pragma nounroll
         for (int jj = blk + 1; jj < kCB; jj++) {
@@ -3900,7 +3631,6 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
           if (old <= me) break;   // (whoever put that value there carries it on to the runs behind)
         }
       }
-#endif
     }
     if (lane == 0) my_arcs += total;
   }
@@ -4187,11 +3917,7 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
         if (l >= link_frame_e) continue;
         if (ks[k] > Dec(rs[k])) x_dst[l] = -1;   // the reference's `continue`: nothing was made of this arc
         else n_acc++;
-#if !defined(KH_NO_NT) && !defined(KH_X_NO_NT_AUX)
         __builtin_nontemporal_store(ords[k] + as[k], &xp_ord[l - link_frame_b]);   // (read once, by pass 2)
-#else
-        xp_ord[l - link_frame_b] = ords[k] + as[k];
-#endif
       }
     }
   }
@@ -4202,11 +3928,7 @@ __device__ bool ProcessEmittingExact(const Utt &u, const Params &p, int frame, i
   // ---- pass 2: FindOrAddToken + minimum cost in the LDS token table, as in the canonical sweep (every live candidate
   // has been accepted: no cutoff test)
   // (the insertion keys inside pass 2 when the ordinals fit its 19 bits - every frame of the benchmark; else the sweep below)
-#ifndef KH_X_NO_FUSED_KEYS
   const bool fuse_ord = run_sum <= 0x7FFFF && p.exact_order == 1;   // (exact_order 2, KH_DECODER_ORDER_SORT: round 4's constructions throughout - the tests)
-#else
-  const bool fuse_ord = false;
-#endif
   if (!EmitPass2<true>(u, sh, nb, tok_limit, link_frame_b, link_frame_e, inf, n_acc, fuse_ord)) return false;
   XS(63);
   // ---- the insertion key of a new token = the smallest ordinal among its candidates (the arc that made the reference
@@ -4707,13 +4429,8 @@ __device__ void PruneFrameLdsBig(const Utt &u, const Params &p, int b, int e, in
     float kk[kBU];
     const bool full = l0 + kBU <= me;
     if (full) {
-#ifndef KH_NO_NT
       const KhInt4 d4 = Load4I_NT(u.link_dst, l0), s4 = Load4I_NT(u.link_src, l0);
       const KhFloat4 k4 = Load4F_NT(u.link_k, l0);
-#else
-      const KhInt4 d4 = Load4I(u.link_dst, l0), s4 = Load4I(u.link_src, l0);
-      const KhFloat4 k4 = Load4F(u.link_k, l0);
-#endif
       dst[0] = d4.x; dst[1] = d4.y; dst[2] = d4.z; dst[3] = d4.w;
       src[0] = s4.x; src[1] = s4.y; src[2] = s4.z; src[3] = s4.w;
       kk[0] = k4.x; kk[1] = k4.y; kk[2] = k4.z; kk[3] = k4.w;
@@ -4916,9 +4633,9 @@ __device__ __forceinline__ void SurvAddLink(const Utt &u, Blk &sh, int l, int f)
 __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb, int fe, Blk &sh) {
   // the pass's own copies of the pointers it uses (see ProcessEmitting: kept in scalar registers for its duration)
   Utt u = u_in;
-  KH_LAUNDER_FB(u.link_dst.p); KH_LAUNDER_FB(u.link_src.p); KH_LAUNDER_FB(u.link_k.p); KH_LAUNDER_FB(u.tok_extra.p); KH_LAUNDER_FB(u.tok_state.p);
-  KH_LAUNDER_FB(u.tok_cost.p); KH_LAUNDER_FB(u.surv_tok.p); KH_LAUNDER_FB(u.surv_link.p);
-  KH_LAUNDER_FB(u.feps_b.p); KH_LAUNDER_FB(u.feps_e.p); KH_LAUNDER_FB(u.femit_b.p); KH_LAUNDER_FB(u.femit_e.p); KH_LAUNDER_FB(u.frame_b.p); KH_LAUNDER_FB(u.frame_e.p);
+  LaunderOne(u.link_dst.p); LaunderOne(u.link_src.p); LaunderOne(u.link_k.p); LaunderOne(u.tok_extra.p); LaunderOne(u.tok_state.p);
+  LaunderOne(u.tok_cost.p); LaunderOne(u.surv_tok.p); LaunderOne(u.surv_link.p);
+  LaunderOne(u.feps_b.p); LaunderOne(u.feps_e.p); LaunderOne(u.femit_b.p); LaunderOne(u.femit_e.p); LaunderOne(u.frame_b.p); LaunderOne(u.frame_e.p);
   const float inf = INFINITY, lb = p.lattice_beam;
   const int t = KH_TIDX;
   auto x_lo = LdsVals(sh);
@@ -4972,13 +4689,8 @@ __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb
       int dst[kBU], src[kBU];
       float kk[kBU];
       if (l0 + kBU <= me) {
-#ifndef KH_NO_NT
         const KhInt4 d4 = Load4I_NT(u.link_dst, l0), s4 = Load4I_NT(u.link_src, l0);   // (the utterance's last pass over its links)
         const KhFloat4 k4 = Load4F_NT(u.link_k, l0);
-#else
-        const KhInt4 d4 = Load4I(u.link_dst, l0), s4 = Load4I(u.link_src, l0);
-        const KhFloat4 k4 = Load4F(u.link_k, l0);
-#endif
         dst[0] = d4.x; dst[1] = d4.y; dst[2] = d4.z; dst[3] = d4.w;
         src[0] = s4.x; src[1] = s4.y; src[2] = s4.z; src[3] = s4.w;
         kk[0] = k4.x; kk[1] = k4.y; kk[2] = k4.z; kk[3] = k4.w;
@@ -6132,12 +5844,8 @@ ServeKernel(const Utt *__restrict__ slots, SlotState *__restrict__ states, Serve
       // polling every 3.4 us are 75 M reads a second in front of the packets the command processor fetches for the host's
       // own kernels (the forward pass of the next chunk): a stream that has polled in vain a few times waits 14, then 27 us
       // between polls (a chunk is 1.5 - 4 ms of work away; the first polls after an action stay at full rate).
-#ifndef KH_SERVE_NO_BACKOFF
       idle_polls++;
       const int reps = idle_polls < 8 ? 1 : (idle_polls < 32 ? 4 : 8);
-#else
-      const int reps = 1;
-#endif
       for (int r = 0; r < reps; r++) __builtin_amdgcn_s_sleep(127);
       continue;
     }

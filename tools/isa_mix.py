@@ -12,14 +12,15 @@ mangled name).
 What to watch when changing the decoder: scratch bytes of DecodeKernel<1,0> (132 at the end of round 4) - every build that
 raised it by 8-24 bytes lost 4-12 % on the GPU."""
 import collections
+import importlib
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-result",
-         "-D__HIP_PLATFORM_AMD__", "-mllvm", "-amdgpu-inline-max-bb=100000", "-mllvm", "-disable-machine-licm", "--cuda-device-only", "-S"]
+sys.path.insert(0, ROOT)
+build = importlib.import_module("old-kaldi-git_amd.build")   # the library's flags, per file: one list, kept there
 
 
 def main():
@@ -31,7 +32,7 @@ def main():
     os.makedirs(objdir, exist_ok=True)
     out = os.path.join(objdir, os.path.basename(path) + ".s")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc] + FLAGS + defs + [path, "-o", out], check=True, stderr=subprocess.DEVNULL)
+    subprocess.run([hipcc] + build.flags_for(path) + ["--cuda-device-only", "-S"] + defs + [path, "-o", out], check=True, stderr=subprocess.DEVNULL)
     kernels, cur = {}, None
     for line in open(out):
         m = re.match(r"^(_Z\w+):", line)

@@ -755,6 +755,45 @@ int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_offsets, const
 int kh_compact_lattice_prune_set_workspace_limit(size_t bytes);
 int kh_compact_lattice_prune_last_timings(float *ms5, int32_t *n_launches);
 
+/* The oracle path of latbin/lattice-oracle.cc:313-421 for a batch of top-sorted CompactLattices, one reference word
+ * sequence each and n_points mask points in one call (csrc/kh_latoracle.hip), with the numerator of CompactLatticeDepth
+ * (lat/lattice-functions.cc:574-602) as a by-product.  HOST CSR and lat_start as kh_compact_lattice_prune takes them;
+ * is_final[s] != 0: the state has a final weight; ref_offsets[n_lats + 1], ref_words: the references; wildcards:
+ * n_wildcards labels in ascending order.  Label 0 and the wildcards are epsilon on the lattice's arcs, and such words are
+ * dropped from the reference (MapWildCards :58-75, :88, :333).  arc_keep, state_keep, final_keep: the masks of
+ * kh_compact_lattice_prune in its layout (W = ceil(n_points / 64) words per arc or state), all three or none; NULL means
+ * n_points = 1 and everything is kept.  Per lattice and point, over the kept arcs, with r[1..R] the reference:
+ * D[start][j] = j; D[e][j] = min(over the arcs s -> e with word w: D[s][j] when w is epsilon, else D[s][j-1] + (w != r[j])
+ * and D[s][j] + 1; D[e][j-1] + 1), int32; errors[l n_points + p] = min D[f][R] over the states whose final weight is kept,
+ * or -1 when no such state is reachable (the reference's "Best-path failed" :359-361).  counts[4 (l n_points + p) + 0..3] =
+ * correct, substitutions, insertions, deletions along one best path (CountErrors :131-164), path_len / path_arcs (arc
+ * numbers relative to the lattice's first arc, written at path_offsets[l n_points + p]; room for n_states - 1 arcs always
+ * suffices) / path_final_state as kh_compact_lattice_best_paths gives them, path_len = -1 for no path; the oracle word
+ * sequence is the non-epsilon labels of those arcs in order.  errors, R = correct + substitutions + deletions and so the
+ * "Overall %WER" total are fixed by the problem and equal the reference's.  WHICH of several equal-cost paths is reported -
+ * the split into insertions, deletions and substitutions, and the word sequence - is in the reference the choice of
+ * fst::ShortestPath over the composed machine (:351-356), which is not reproduced; the rule here is: the lowest-numbered
+ * end state that attains the minimum, then, walking back, the first candidate that attains the cell's value among the
+ * incoming kept arcs in ascending arc number (for an arc with a word its diagonal before its insertion) and the deletion
+ * last.  arc_frames[a], final_frames[s] (both or neither; may be NULL): the lengths of the transition-id strings;
+ * arc_frame_sum[l n_points + p] = their sum over the kept arcs and over the kept finals of surviving states
+ * (lattice-functions.cc:593-600 on the pruned lattice).  KH_EINVAL, with the arc, state or point named, for an arc to a
+ * state that is not higher-numbered, lat_start out of range, n_points < 1 (or > 1 without masks), ref_offsets that do not
+ * ascend, a reference of 2^24 = 16777216 words or more (the limit of this call), path room below n_states - 1.  The workspace is n_states x (R + 1) x 4 bytes per lattice and point in flight;
+ * lattices are taken longest first, as many per launch as half of the free device memory admits, or as
+ * kh_compact_lattice_oracle_set_workspace_limit(bytes) admits: a setting of the CALLING THREAD (0 = back to automatic; one
+ * lattice always runs).  kh_compact_lattice_oracle_last_timings: as kh_compact_lattice_prune_last_timings. */
+int kh_compact_lattice_oracle(int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start,
+                              const int64_t *arc_offsets, const int32_t *arc_label, const int32_t *arc_nextstate,
+                              const int32_t *is_final, const int64_t *ref_offsets, const int32_t *ref_words,
+                              int n_wildcards, const int32_t *wildcards, int n_points, const uint64_t *arc_keep,
+                              const uint64_t *state_keep, const uint64_t *final_keep, const int32_t *arc_frames,
+                              const int32_t *final_frames, int32_t *errors, int32_t *counts, int32_t *path_len,
+                              int32_t *path_arcs, const int64_t *path_offsets, int32_t *path_final_state,
+                              int64_t *arc_frame_sum);
+int kh_compact_lattice_oracle_set_workspace_limit(size_t bytes);
+int kh_compact_lattice_oracle_last_timings(float *ms5, int32_t *n_launches);
+
 /* LatticeForwardBackwardMpeVariants (lat/lattice-functions.cc:740-919): criterion
  * "smbr" (is_mpfe = 0) or "mpfe".  tid2phone / tid2pdf = TransitionIdToPhone /
  * TransitionIdToPdf as arrays of num_tids + 1 entries indexed by transition-id;

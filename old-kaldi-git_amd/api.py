@@ -1504,8 +1504,9 @@ def compact_lattice_prune_raw(csrs, starts, points, beams, workspace_limit=None)
     """kh_compact_lattice_prune on CSR dicts (compact_lattice_to_prune_csr's layout, top-sorted), starts = the start state
     of each, points as compact_lattice_best_paths_raw takes them, beams = one float or one per point.  Returns
     dict(arc_keep, state_keep, final_keep = bool [arcs or states of the whole batch x n_points], best_final_cost
-    [n_lats x n_points], state_offsets, arc_offsets = where each lattice's rows begin).  workspace_limit as
-    compact_lattice_best_paths_raw's."""
+    [n_lats x n_points], state_offsets, arc_offsets = where each lattice's rows begin, and arc_keep_words, state_keep_words,
+    final_keep_words = the same masks as the call wrote them: uint64 [arcs or states x ceil(n_points / 64)], bit p % 64 of
+    word p / 64).  workspace_limit as compact_lattice_best_paths_raw's."""
     n, K = len(csrs), len(points)
     if n == 0 or K == 0:
         raise KhError("compact_lattice_prune: no lattices or no score points")
@@ -1543,7 +1544,8 @@ def compact_lattice_prune_raw(csrs, starts, points, beams, workspace_limit=None)
     # bit p % 64 of word p / 64 -> column p (the words are little-endian: byte p / 8, bit p % 8)
     bits = lambda m: np.unpackbits(m.astype("<u8").view(np.uint8).reshape(len(m), 8 * W), axis=1, bitorder="little")[:, :K].astype(bool)
     return dict(arc_keep=bits(akeep), state_keep=bits(skeep), final_keep=bits(fkeep), best_final_cost=best,
-                state_offsets=soff.astype(np.int64), arc_offsets=lat_arc_off)
+                state_offsets=soff.astype(np.int64), arc_offsets=lat_arc_off, arc_keep_words=akeep, state_keep_words=skeep,
+                final_keep_words=fkeep)
 
 
 def _apply_score_point(g, a, label, scale, penalty):
@@ -1633,6 +1635,210 @@ def compact_lattice_prune_last_timings():
     ms = (C.c_float * 5)()
     n = C.c_int32()
     check(lib().kh_compact_lattice_prune_last_timings(ms, C.byref(n)))
+    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
+
+
+# ---------------------------------------------------------------- oracle path and depth (csrc/kh_latoracle.hip)
+def _mask_words(m, K):
+    """bool [n x K] -> the uint64 words of kh_compact_lattice_prune's masks [n x ceil(K / 64)]."""
+    m = np.asarray(m, bool).reshape(-1, K)
+    W = (K + 63) // 64
+    b = np.zeros((len(m), 8 * W), np.uint8)
+    packed = np.packbits(m, axis=1, bitorder="little")
+    b[:, :packed.shape[1]] = packed
+    return np.ascontiguousarray(b.view("<u8").astype(np.uint64).reshape(len(m), W))
+
+
+def _csr_is_final(L):
+    if "is_final" in L:
+        return np.asarray(L["is_final"], bool)
+    fg, fa = np.asarray(L["final_graph"], np.float32), np.asarray(L["final_acoustic"], np.float32)
+    return ~((fg == np.inf) & (fa == np.inf))          # Final(s) != Weight::Zero()
+
+
+def compact_lattice_oracle_raw(csrs, starts, refs, wildcards, masks=None, workspace_limit=None):
+    """kh_compact_lattice_oracle on CSR dicts (compact_lattice_to_prune_csr's layout, top-sorted), starts = the start state
+    of each, refs = one integer sequence per lattice, wildcards = labels that count as epsilon.  masks: None (one point,
+    everything kept) or dict(arc_keep, state_keep, final_keep = bool [arcs or states of the whole batch x n_points]) as
+    compact_lattice_prune_raw returns; where the dict also carries its arc_keep_words, state_keep_words, final_keep_words
+    those go to the device as they are and the bool arrays are not packed again.  When every dict carries arc_frames and final_frames (the lengths of the
+    transition-id strings) the frame sums are returned too.  Returns dict(errors [n_lats x n_points], counts
+    [n_lats x n_points x 4: correct, sub, ins, del], path_len, paths [list of lists of int32 arrays: CSR arc numbers
+    within the lattice], final_state, frame_sum [int64, or None])."""
+    n = len(csrs)
+    if n == 0 or len(refs) != n:
+        raise KhError("compact_lattice_oracle: no lattices, or not one reference per lattice")
+    K = 1 if masks is None else int(np.asarray(masks["final_keep"]).shape[1])
+    soff = np.zeros(n + 1, np.int32)
+    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
+    aoff, base = [np.zeros(1, np.int64)], 0
+    for L in csrs:
+        o = np.asarray(L["arc_offsets"], np.int64)
+        aoff.append(o[1:] + base)
+        base += int(o[-1])
+    aoff = np.ascontiguousarray(np.concatenate(aoff))
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt) for L in csrs]))
+    lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
+    fin = np.ascontiguousarray(np.concatenate([_csr_is_final(L) for L in csrs]).astype(np.int32))
+    st = np.ascontiguousarray(np.asarray(starts, np.int32).reshape(n))
+    roff = np.zeros(n + 1, np.int64)
+    roff[1:] = np.cumsum([len(r) for r in refs])
+    rw = np.ascontiguousarray(np.concatenate([np.asarray(r, np.int32).reshape(-1) for r in refs] + [np.zeros(0, np.int32)]))
+    wild = np.ascontiguousarray(np.unique(np.asarray(list(wildcards), np.int32)))
+    frames = all("arc_frames" in L and "final_frames" in L for L in csrs)
+    af, ff = (cat("arc_frames", np.int32), cat("final_frames", np.int32)) if frames else (None, None)
+    ip, up, lp = capi.c_int32_p, capi.c_uint64_p, capi.c_int64_p
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    ak = sk = fk = None
+    if masks is not None:
+        W = (K + 63) // 64
+        words = lambda k, rows: (np.ascontiguousarray(np.asarray(masks[k + "_words"], np.uint64).reshape(rows, W))
+                                 if k + "_words" in masks else _mask_words(masks[k], K))
+        ak, sk, fk = words("arc_keep", len(lab)), words("state_keep", int(soff[-1])), words("final_keep", int(soff[-1]))
+        if not (len(ak) == len(lab) and len(sk) == len(fk) == int(soff[-1])):
+            raise KhError("compact_lattice_oracle: the masks have %d, %d, %d rows for %d arcs and %d states"
+                          % (len(ak), len(sk), len(fk), len(lab), int(soff[-1])))
+    room = np.repeat(np.maximum(np.diff(soff).astype(np.int64) - 1, 1), K)      # a path has at most n_states - 1 arcs
+    poff = np.zeros(n * K + 1, np.int64)
+    poff[1:] = np.cumsum(room)
+    err, cnt = np.empty(n * K, np.int32), np.empty(n * K * 4, np.int32)
+    plen, pfin = np.empty(n * K, np.int32), np.empty(n * K, np.int32)
+    parcs = np.empty(int(poff[-1]), np.int32)
+    fsum = np.zeros(n * K, np.int64)
+    if workspace_limit is not None:
+        check(lib().kh_compact_lattice_oracle_set_workspace_limit(int(workspace_limit)))
+    try:
+        check(lib().kh_compact_lattice_oracle(
+            n, ptr(soff, ip), ptr(st, ip), ptr(aoff, lp), ptr(lab, ip), ptr(ns, ip), ptr(fin, ip), ptr(roff, lp), ptr(rw, ip),
+            len(wild), ptr(wild, ip), K, ptr(ak, up), ptr(sk, up), ptr(fk, up), ptr(af, ip), ptr(ff, ip), ptr(err, ip),
+            ptr(cnt, ip), ptr(plen, ip), ptr(parcs, ip), ptr(poff, lp), ptr(pfin, ip), ptr(fsum, lp) if frames else None))
+    finally:
+        if workspace_limit is not None:
+            check(lib().kh_compact_lattice_oracle_set_workspace_limit(0))
+    paths = [[parcs[poff[i * K + p]:poff[i * K + p] + max(int(plen[i * K + p]), 0)].copy() for p in range(K)] for i in range(n)]
+    return dict(errors=err.reshape(n, K), counts=cnt.reshape(n, K, 4), path_len=plen.reshape(n, K), paths=paths,
+                final_state=pfin.reshape(n, K), frame_sum=fsum.reshape(n, K) if frames else None)
+
+
+def _prune_csr_state_times(L):
+    """CompactLatticeStateTimes (lat/lattice-functions.cc:69-106) on a CSR dict with arc_frames, counted from its start
+    state: times [-1 = not reachable].  Raises where the reference's assertion :87 fails."""
+    n, start = int(L["n_states"]), int(L["start"])
+    off, nxt, af = np.asarray(L["arc_offsets"], np.int64), np.asarray(L["arc_nextstate"], np.int64), np.asarray(L["arc_frames"], np.int64)
+    times = np.full(n, -1, np.int64)
+    times[start] = 0
+    for s in range(start, n):
+        if times[s] < 0 or off[s] == off[s + 1]:
+            continue
+        d, t = nxt[off[s]:off[s + 1]], times[s] + af[off[s]:off[s + 1]]
+        unset = times[d] < 0
+        times[d[unset]] = t[unset]
+        if not np.array_equal(times[d], t):
+            raise KhError("KALDI_ASSERT: at CompactLatticeStateTimes:lattice-functions.cc:87, failed: "
+                          "(*times)[arc.nextstate] == cur_time + arc_len")
+    return times
+
+
+def _oracle_csr(clat):
+    """compact_lattice_to_prune_csr plus is_final and, when the dict carries the strings, arc_frames / final_frames."""
+    L = compact_lattice_to_prune_csr(clat)
+    L["is_final"] = _csr_is_final(L)
+    if "arc_string" in clat and "final_string" in clat:
+        L["arc_frames"] = np.asarray([len(clat["arc_string"][j]) for j in L["perm"]], np.int32).reshape(-1)
+        L["final_frames"] = np.asarray([len(clat["final_string"][s]) for s in L["state_of"]], np.int32).reshape(-1)
+    return L
+
+
+def compact_lattice_depth(clat):
+    """CompactLatticeDepth (lat/lattice-functions.cc:574-602) after TopSortCompactLatticeIfNeeded (latbin/lattice-depth.cc:65):
+    (depth [float32], t) with t from CompactLatticeStateTimes (:69-106).  Depth is 1.0 and t = 0 when there is no start
+    state (:581-584) or no final state is reachable (where the reference divides by zero)."""
+    if int(clat["n_states"]) == 0 or int(clat.get("start", 0)) < 0:
+        return np.float32(1.0), 0
+    L = _oracle_csr(clat)
+    times = _prune_csr_state_times(L)
+    ends = times + L["final_frames"]
+    ok = L["is_final"] & (times >= 0)
+    t = int(ends[ok].max()) if ok.any() else 0
+    if t == 0:
+        return np.float32(1.0), 0
+    num_arc_frames = int(L["arc_frames"].sum(dtype=np.int64)) + int(L["final_frames"].sum(dtype=np.int64))
+    return np.float32(num_arc_frames) / np.float32(t), t
+
+
+def compact_lattice_oracle(clats, refs, wildcards=(), points=None, beams=None, workspace_limit=None):
+    """lattice-oracle (latbin/lattice-oracle.cc:313-421) and lattice-depth for a batch of CompactLattices (dict layout of
+    kaldi_io.read_compact_lattice; without the strings there is no depth) and one reference word sequence each.  With beams
+    (one per point; points = one score_point or one per beam, default the identity) every lattice is first pruned on the
+    device at each beam - `lattice-scale | lattice-prune --beam=b` - and the masks go straight into the oracle call.
+    Returns per lattice a list over the points of dict(errors [-1: no path, the reference's "Best-path failed"], correct,
+    sub, ins, del, words = the oracle word sequence, path_arcs = the path as indices into the dict's arc arrays, depth,
+    num_frames = CompactLatticeDepth of what the point keeps [None without strings]).  errors and
+    correct + sub + del = the reference's length are the reference binary's; which of several equal-cost paths is reported
+    follows the rule in include/kaldi_hip.h, not OpenFst's ShortestPath."""
+    if beams is None:
+        K = 1
+    else:
+        bm = np.asarray(beams, np.float32).reshape(-1)
+        K = len(bm)
+        points = [score_point()] if points is None else list(points)
+        if len(points) == 1:
+            points = points * K
+        if len(points) != K:
+            raise KhError("compact_lattice_oracle: %d score points for %d beams" % (len(points), K))
+    wild = set(int(w) for w in wildcards)
+    none = lambda: dict(errors=-1, correct=0, sub=0, ins=0, words=np.zeros(0, np.int32), path_arcs=np.zeros(0, np.int64),
+                        depth=np.float32(1.0), num_frames=0, **{"del": 0})
+    has_start = [int(c["n_states"]) > 0 and int(c.get("start", 0)) >= 0 for c in clats]
+    csrs = [_oracle_csr(c) for c, ok in zip(clats, has_start) if ok]
+    if not csrs:
+        return [[none() for _ in range(K)] for _ in clats]
+    starts = [L["start"] for L in csrs]
+    masks = None if beams is None else compact_lattice_prune_raw(csrs, starts, points, bm, workspace_limit)
+    raw = compact_lattice_oracle_raw(csrs, starts, [r for r, ok in zip(refs, has_start) if ok], wild, masks, workspace_limit)
+    out = []
+    i, s0 = -1, 0
+    for c, ok in zip(clats, has_start):
+        if not ok:
+            out.append([none() for _ in range(K)])
+            continue
+        i += 1
+        L = csrs[i]
+        n = int(L["n_states"])
+        labels = np.asarray(L["arc_label"], np.int32)
+        eps = (labels == 0) | np.isin(labels, list(wild))
+        ends = None
+        if raw["frame_sum"] is not None:
+            times = _prune_csr_state_times(L)
+            ends = np.where(L["is_final"] & (times >= 0), times + L["final_frames"], 0)
+        row = []
+        for p in range(K):
+            r = none()
+            if ends is not None:
+                live = ends if masks is None else np.where(masks["state_keep"][s0:s0 + n, p] & masks["final_keep"][s0:s0 + n, p], ends, 0)
+                t = int(live.max())
+                if t > 0:
+                    r["depth"], r["num_frames"] = np.float32(int(raw["frame_sum"][i, p])) / np.float32(t), t
+            else:
+                r["depth"] = r["num_frames"] = None
+            if raw["errors"][i, p] >= 0:
+                arcs = raw["paths"][i][p]
+                cnt = raw["counts"][i, p]
+                r.update(errors=int(raw["errors"][i, p]), correct=int(cnt[0]), sub=int(cnt[1]), ins=int(cnt[2]),
+                         words=labels[arcs][~eps[arcs]], path_arcs=L["perm"][arcs].astype(np.int64))
+                r["del"] = int(cnt[3])
+            row.append(r)
+        out.append(row)
+        s0 += n
+    return out
+
+
+def compact_lattice_oracle_last_timings():
+    """Milliseconds the last compact_lattice_oracle call of this thread spent in host preparation / upload / kernel /
+    download (the allocations are in none of the four), in the whole C call, and the number of kernel launches."""
+    ms = (C.c_float * 5)()
+    n = C.c_int32()
+    check(lib().kh_compact_lattice_oracle_last_timings(ms, C.byref(n)))
     return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
 
 

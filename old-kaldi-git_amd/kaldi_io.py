@@ -380,6 +380,8 @@ def _read_object(s, binary, kind):
         return read_lattice(s, binary)
     if kind == "any_lattice":
         return read_any_lattice(s, binary)
+    if kind == "lattice_or_compact":
+        return read_lattice_or_compact(s, binary)
     if kind == "posterior":
         return read_posterior(s, binary)
     raise ValueError("unknown table object kind " + kind)
@@ -406,6 +408,10 @@ def _write_object(f, binary, kind, obj):
         write_posterior(f, obj, binary)
     elif kind == "base_float":
         write_float(f, binary, obj)
+        if not binary:
+            f.write(b"\n")
+    elif kind == "int32":               # BasicHolder<int32>::Write (kaldi-holder-inl.h)
+        write_int32(f, binary, int(obj))
         if not binary:
             f.write(b"\n")
     else:
@@ -1154,10 +1160,9 @@ def compact_lattice_to_lattice(c):
                 state_final_graph=fg, state_final_acoustic=fa)
 
 
-def read_any_lattice(s, binary=True):
-    """LatticeHolder::Read (lat/kaldi-lattice.cc:394-430): the table may hold Lattices or CompactLattices (what
-    `lattice-to-post "ark:gunzip -c lat.1.gz|"` reads is the decoder's CompactLattice output); either comes back as a
-    state-level lattice."""
+def read_lattice_or_compact(s, binary=True):
+    """LatticeHolder::Read (lat/kaldi-lattice.cc:394-430) without the conversion: (True, CompactLattice dict) or
+    (False, Lattice dict), whichever the table holds."""
     s = _as_stream(s)
     if binary:
         head = s.peek(64)
@@ -1165,16 +1170,24 @@ def read_any_lattice(s, binary=True):
         n2 = struct.unpack("<i", head[8 + n1:12 + n1])[0]
         arctype = head[12 + n1:12 + n1 + n2].decode()
         if arctype.startswith("compactlattice"):
-            return compact_lattice_to_lattice(read_compact_lattice(s, True))
-        return read_lattice(s, True)
+            return True, read_compact_lattice(s, True)
+        return False, read_lattice(s, True)
     # text: a CompactLattice is an acceptor - "src dst word g,a,1_2_3" - so its 4th column is the weight (it has commas);
     # the 4th column of a Lattice line is the output label
     look = s.peek(4096).split(b"\n")
     for line in look:
         col = line.split()
         if len(col) >= 4:
-            return compact_lattice_to_lattice(read_compact_lattice(s, False)) if b"," in col[3] else read_lattice(s, False)
-    return read_lattice(s, False)
+            return (True, read_compact_lattice(s, False)) if b"," in col[3] else (False, read_lattice(s, False))
+    return False, read_lattice(s, False)
+
+
+def read_any_lattice(s, binary=True):
+    """LatticeHolder::Read (lat/kaldi-lattice.cc:394-430): the table may hold Lattices or CompactLattices (what
+    `lattice-to-post "ark:gunzip -c lat.1.gz|"` reads is the decoder's CompactLattice output); either comes back as a
+    state-level lattice."""
+    compact, L = read_lattice_or_compact(s, binary)
+    return compact_lattice_to_lattice(L) if compact else L
 
 
 def write_posterior(f, post, binary=True):

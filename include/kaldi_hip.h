@@ -794,6 +794,50 @@ int kh_compact_lattice_oracle(int n_lats, const int32_t *lat_state_offsets, cons
 int kh_compact_lattice_oracle_set_workspace_limit(size_t bytes);
 int kh_compact_lattice_oracle_last_timings(float *ms5, int32_t *n_launches);
 
+/* MinimumBayesRisk (lat/sausages.{h,cc}), the class behind lattice-mbr-decode and lattice-to-ctm-conf, for a batch of
+ * top-sorted CompactLattices and n_points score points in one call (csrc/kh_latmbr.hip).  HOST CSR, lat_start, scales and
+ * penalties as kh_compact_lattice_prune takes them; the lattices are in the class's own form (PrepareLatticeAndInitStats
+ * :268-315): lat_start = 0, the last state the single final state with weight One (0, 0) and no arcs, every other final
+ * weight Zero (+inf, +inf); state_times[s] = CompactLatticeStateTimes.  hyp_words at hyp_offsets[l n_points + p]: the
+ * initial R_ of the pair (the constructors' :342 / :358); do_mbr as the class's flag.  Per lattice and point, restating
+ * sausages.cc:27-266 statement by statement: each weight scaled as kh_compact_lattice_best_paths documents, loglike =
+ * -(g' + a') summed in float (:306-307), l() and delta() of sausages.h:110,132 (delta is the float 1.0e-05 promoted to
+ * double).  The transcendentals are taken on the host with libm: alpha(n) by the double LogAdd of base/kaldi-math.h:178-195
+ * in pre_[n] order and w_a = exp(alpha(s_a) + p_a - alpha(n)) per arc; the kernel (one AccStats() per launch, one wave per
+ * pair still iterating) does only double +, *, comparisons and integer work in the reference's order, so the results are
+ * the restatement's bits.  The one deliberate difference: a state other than the start with alpha = -inf, where :125
+ * computes exp(NaN), is refused.
+ * Outputs (HOST), entry o = l n_points + p: n_words[o] and words / one_best_confidences at word_offsets[o], one_best_times
+ * (pairs) at 2 word_offsets[o]: R_ without epsilons (:68), one_best_confidences_, one_best_times_; bayes_risk[o] = L_
+ * (double; GetBayesRisk narrows it to float); iterations[o] = AccStats() calls; the last iteration's bins: n_bins[o] and
+ * bin_sizes / bin_times (pairs, after the averaging of :257-264) at bin_offsets[o] / 2 bin_offsets[o]; n_stats[o] and
+ * gamma_ as stat_words / stat_post at stat_offsets[o], the bins one after the other, each sorted by GammaCompare.  The three
+ * offset arrays (n_lats n_points + 1 entries) are the room the caller leaves; n_words, n_bins and n_stats are always
+ * written, and KH_EINVAL is returned - nothing else written - when a pair does not fit, so a second call with the room they
+ * name succeeds.  KH_EINVAL, with the state, arc or point named, also for an arc to a state that is not higher-numbered, a
+ * start state other than 0, a last state that is not the single final state with weight One, a NaN or -inf weight (before
+ * or after the point is applied), alpha = -inf as above, n_points < 1.
+ * The workspace per pair in flight is 2 x n_states x (Q + 1) x 8 bytes (alpha_dash, beta_dash) + (Q + 1) x 4 (b_arc) +
+ * (V + 2) x (Q + 1) x 8 (gamma, dense, V = the lattice's distinct arc labels plus 0; tau_b, tau_e), Q = 2 |R_| + 1 of the
+ * current iteration; pairs are taken largest first, as many per launch as half of the free device memory admits, or as
+ * kh_compact_lattice_mbr_set_workspace_limit(bytes) admits: a setting of the CALLING THREAD (0 = back to automatic; one
+ * pair always runs).  kh_compact_lattice_mbr_last_timings: milliseconds the last call of this thread spent in { host
+ * preparation (validation, incoming-arc lists, alpha and w_a), uploads, kernels with their memsets, downloads (HIP
+ * events), the whole call by the host's clock, the host's part of MbrDecode (casting and sorting gamma, updating R_) },
+ * and counts3 (may be NULL) = { kernel launches, rounds of the host loop = the largest iteration count, AccStats() calls
+ * summed over the pairs }. */
+int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start,
+                           const int64_t *arc_offsets, const int32_t *arc_label, const int32_t *arc_nextstate,
+                           const float *arc_graph, const float *arc_acoustic, const float *final_graph,
+                           const float *final_acoustic, const int32_t *state_times, int n_points, const double *scales,
+                           const float *penalties, const int64_t *hyp_offsets, const int32_t *hyp_words, int do_mbr,
+                           int32_t *n_words, const int64_t *word_offsets, int32_t *words, float *one_best_times,
+                           float *one_best_confidences, double *bayes_risk, int32_t *iterations, int32_t *n_bins,
+                           const int64_t *bin_offsets, int32_t *bin_sizes, float *bin_times, int32_t *n_stats,
+                           const int64_t *stat_offsets, int32_t *stat_words, float *stat_post);
+int kh_compact_lattice_mbr_set_workspace_limit(size_t bytes);
+int kh_compact_lattice_mbr_last_timings(float *ms6, int32_t *counts3);
+
 /* LatticeForwardBackwardMpeVariants (lat/lattice-functions.cc:740-919): criterion
  * "smbr" (is_mpfe = 0) or "mpfe".  tid2phone / tid2pdf = TransitionIdToPhone /
  * TransitionIdToPdf as arrays of num_tids + 1 entries indexed by transition-id;

@@ -1842,6 +1842,179 @@ def compact_lattice_oracle_last_timings():
     return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
 
 
+# ---------------------------------------------------------------- minimum Bayes risk decoding (csrc/kh_latmbr.hip)
+def compact_lattice_mbr_prepare(clat):
+    """PrepareLatticeAndInitStats (lat/sausages.cc:268-315) on a CompactLattice dict (layout of
+    kaldi_io.read_compact_lattice, with the strings): CreateSuperFinal by its own rule
+    (fstext/pre-determinize-inl.h:693-730: a single final state with weight One and no arcs is left alone; otherwise a new
+    last state becomes the only final state, and every old final state gets, in ascending state order, an epsilon arc to it
+    that carries its final weight, appended behind its other arcs); then the states are renumbered by
+    compact_lattice_top_order, only if the result is not sorted as it stands; then CompactLatticeStateTimes.  Returns the
+    CSR dict of compact_lattice_to_csr plus start = 0, arc_frames, state_times (int32; -1 = not reachable), and
+    n_input_arcs (CSR arcs whose perm is >= that are the added ones).  Raises where the reference would fail (a cycle,
+    inconsistent times) and where the last state does not come out as the single final state - the reference assumes it
+    (:323-327), which holds for a lattice without dead ends."""
+    n = int(clat["n_states"])
+    fg, fa = np.asarray(clat["final_g"], np.float32), np.asarray(clat["final_a"], np.float32)
+    src, dst = np.asarray(clat["arc_src"], np.int64), np.asarray(clat["arc_dst"], np.int64)
+    finals = np.flatnonzero(~((fg == np.inf) & (fa == np.inf)))                          # :701-706
+    n_in = len(src)
+    aug = dict(clat)
+    single = len(finals) == 1 and fg[finals[0]] == 0 and fa[finals[0]] == 0 and len(clat["final_string"][finals[0]]) == 0 \
+        and not np.any(src == finals[0])                                                # :707-714
+    if not single:
+        empty = np.zeros(0, np.int32)
+        k = len(finals)
+        new_fg, new_fa = np.full(n + 1, np.inf, np.float32), np.full(n + 1, np.inf, np.float32)
+        new_fg[n] = new_fa[n] = 0.0                                                      # :716-717
+        fstr = [empty for _ in range(n + 1)]
+        aug.update(n_states=n + 1, arc_src=np.concatenate([src, finals]).astype(np.int32),          # :718-728
+                   arc_dst=np.concatenate([dst, np.full(k, n, np.int64)]).astype(np.int32),
+                   arc_label=np.concatenate([np.asarray(clat["arc_label"], np.int32), np.zeros(k, np.int32)]),
+                   arc_g=np.concatenate([np.asarray(clat["arc_g"], np.float32), fg[finals]]),
+                   arc_a=np.concatenate([np.asarray(clat["arc_a"], np.float32), fa[finals]]),
+                   arc_string=list(clat["arc_string"]) + [np.asarray(clat["final_string"][s], np.int32) for s in finals],
+                   final_g=new_fg, final_a=new_fa, final_string=fstr)
+    if int(aug["n_states"]) == 0 or int(aug.get("start", 0)) < 0:
+        raise KhError("compact_lattice_mbr_prepare: the lattice has no start state")
+    L = compact_lattice_to_csr(aug)                                                      # :276-280
+    L["start"] = 0
+    L["arc_frames"] = np.asarray([len(aug["arc_string"][j]) for j in L["perm"]], np.int32).reshape(-1)
+    L["state_times"] = _prune_csr_state_times(L).astype(np.int32)                        # :281
+    L["n_input_arcs"] = n_in
+    N = int(L["n_states"])
+    is_final = _csr_is_final(L)
+    if not (is_final[N - 1] and is_final.sum() == 1 and L["arc_offsets"][N - 1] == L["arc_offsets"][N]):
+        raise KhError("compact_lattice_mbr_prepare: after the topological sort the final state is state %s of %d, not the "
+                      "last one (the lattice has dead ends; the reference assumes it has none, lat/sausages.cc:323-327)"
+                      % (np.flatnonzero(is_final).tolist(), N))
+    return L
+
+
+def compact_lattice_mbr_raw(csrs, points, hyps, do_mbr=True, workspace_limit=None):
+    """kh_compact_lattice_mbr on prepared CSR dicts (compact_lattice_mbr_prepare), points as compact_lattice_best_paths_raw
+    takes them, hyps[i][p] = the initial word sequence of lattice i at point p.  Returns a list per lattice of a list per
+    point of dict(words [int32], bayes_risk [float64, L_], iterations, sausage_stats [list over the bins of lists of
+    (word, float32)], sausage_times, one_best_times [float32 n x 2], one_best_confidences [float32]).  The room for the
+    ragged outputs is a guess from the hypotheses; when a pair does not fit, the call is made once more with the room the
+    first one reported."""
+    n, K = len(csrs), len(points)
+    if n == 0 or K == 0:
+        raise KhError("compact_lattice_mbr: no lattices or no score points")
+    soff = np.zeros(n + 1, np.int32)
+    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
+    aoff, base = [np.zeros(1, np.int64)], 0
+    for L in csrs:
+        o = np.asarray(L["arc_offsets"], np.int64)
+        aoff.append(o[1:] + base)
+        base += int(o[-1])
+    aoff = np.ascontiguousarray(np.concatenate(aoff))
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt).reshape(-1) for L in csrs]))
+    lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
+    g, a = cat("arc_graph", np.float32), cat("arc_acoustic", np.float32)
+    fg, fa = cat("final_graph", np.float32), cat("final_acoustic", np.float32)
+    times = cat("state_times", np.int32)
+    st = np.ascontiguousarray(np.asarray([int(L.get("start", 0)) for L in csrs], np.int32))
+    scales = np.ascontiguousarray(np.stack([np.asarray(s, np.float64).reshape(4) for s, _ in points]))
+    pens = np.ascontiguousarray(np.asarray([p for _, p in points], np.float32))
+    flat = [np.asarray(hyps[i][p], np.int32).reshape(-1) for i in range(n) for p in range(K)]
+    hoff = np.zeros(n * K + 1, np.int64)
+    hoff[1:] = np.cumsum([len(h) for h in flat])
+    hw = np.ascontiguousarray(np.concatenate(flat + [np.zeros(0, np.int32)]))
+    n_labels = np.repeat([len(np.unique(L["arc_label"])) + 1 for L in csrs], K)
+    nw, nb, nst = np.zeros(n * K, np.int32), np.zeros(n * K, np.int32), np.zeros(n * K, np.int32)
+    risk, iters = np.zeros(n * K, np.float64), np.zeros(n * K, np.int32)
+    room_w = np.diff(hoff) + 8
+    room_b = 2 * room_w + 1
+    room_s = room_b * np.minimum(n_labels, 32)
+    ip, fp, lp, dp = capi.c_int32_p, capi.c_float_p, capi.c_int64_p, capi.c_double_p
+    ptr = lambda x, t: x.ctypes.data_as(t)
+    offs = lambda room: np.ascontiguousarray(np.concatenate([[0], np.cumsum(room)]).astype(np.int64))
+    if workspace_limit is not None:
+        check(lib().kh_compact_lattice_mbr_set_workspace_limit(int(workspace_limit)))
+    try:
+        for attempt in range(2):
+            woff, boff, soff2 = offs(room_w), offs(room_b), offs(room_s)
+            words, obt, obc = np.zeros(int(woff[-1]), np.int32), np.zeros(2 * int(woff[-1]), np.float32), np.zeros(int(woff[-1]), np.float32)
+            bsz, bt = np.zeros(int(boff[-1]), np.int32), np.zeros(2 * int(boff[-1]), np.float32)
+            sw, sp = np.zeros(int(soff2[-1]), np.int32), np.zeros(int(soff2[-1]), np.float32)
+            rc = lib().kh_compact_lattice_mbr(
+                n, ptr(soff, ip), ptr(st, ip), ptr(aoff, lp), ptr(lab, ip), ptr(ns, ip), ptr(g, fp), ptr(a, fp), ptr(fg, fp),
+                ptr(fa, fp), ptr(times, ip), K, ptr(scales, dp), ptr(pens, fp), ptr(hoff, lp), ptr(hw, ip), 1 if do_mbr else 0,
+                ptr(nw, ip), ptr(woff, lp), ptr(words, ip), ptr(obt, fp), ptr(obc, fp), ptr(risk, dp), ptr(iters, ip),
+                ptr(nb, ip), ptr(boff, lp), ptr(bsz, ip), ptr(bt, fp), ptr(nst, ip), ptr(soff2, lp), ptr(sw, ip), ptr(sp, fp))
+            if rc != 0 and attempt == 0 and b"do not fit the room" in lib().kh_last_error():
+                room_w, room_b, room_s = nw.astype(np.int64), nb.astype(np.int64), nst.astype(np.int64)
+                continue
+            check(rc)
+            break
+    finally:
+        if workspace_limit is not None:
+            check(lib().kh_compact_lattice_mbr_set_workspace_limit(0))
+    out = []
+    for i in range(n):
+        row = []
+        for p in range(K):
+            o = i * K + p
+            w0, b0, s0 = int(woff[o]), int(boff[o]), int(soff2[o])
+            sizes = bsz[b0:b0 + nb[o]]
+            ends = s0 + np.cumsum(sizes)
+            stats = [list(zip(sw[e - k:e].tolist(), sp[e - k:e])) for k, e in zip(sizes.tolist(), ends.tolist())]
+            row.append(dict(words=words[w0:w0 + nw[o]].copy(), bayes_risk=float(risk[o]), iterations=int(iters[o]),
+                            sausage_stats=stats, sausage_times=bt[2 * b0:2 * (b0 + nb[o])].reshape(-1, 2).copy(),
+                            one_best_times=obt[2 * w0:2 * (w0 + nw[o])].reshape(-1, 2).copy(),
+                            one_best_confidences=obc[w0:w0 + nw[o]].copy()))
+        out.append(row)
+    return out
+
+
+def compact_lattice_mbr(clats, points=None, one_bests=None, do_mbr=True, workspace_limit=None):
+    """MinimumBayesRisk (lat/sausages.{h,cc}: lattice-mbr-decode, lattice-to-ctm-conf) for a batch of CompactLattices (dict
+    layout of kaldi_io.read_compact_lattice, with the strings) and a list of score points (score_point; None = the lattice
+    as it is) in ONE call.  one_bests: None, or per lattice a word sequence that is the initial hypothesis at every point
+    (the class's second constructor; lattice-to-ctm-conf's three-argument form passes do_mbr=False with it).  Without it the
+    initial hypothesis is the word sequence of compact_lattice_best_paths on the prepared lattice at the same points.  The
+    reference takes fst::ShortestPath there (:329-345); both find a path of the smallest cost, but where best paths tie in
+    cost they may return different ones, and the initial hypothesis - and with do_mbr=False the result - may then differ.
+    Returns per lattice a list over the points of dict(words [int32, GetOneBest], bayes_risk [float32, GetBayesRisk],
+    sausage_stats [per bin a list of (word, float32), most likely first], sausage_times, one_best_times [float32 n x 2],
+    one_best_confidences [float32], iterations); None for every point of a lattice without states or start state."""
+    points = [score_point()] if points is None else list(points)
+    K = len(points)
+    has_start = [int(c["n_states"]) > 0 and int(c.get("start", 0)) >= 0 for c in clats]
+    csrs = [compact_lattice_mbr_prepare(c) for c, ok in zip(clats, has_start) if ok]
+    if not csrs:
+        return [[None] * K for _ in clats]
+    if one_bests is None:
+        plen, paths, _, _, _ = compact_lattice_best_paths_raw(csrs, points, workspace_limit)
+        hyps = []
+        for i, L in enumerate(csrs):
+            if np.any(plen[i] < 0):
+                raise KhError("compact_lattice_mbr: lattice %d has no path to its final state" % i)
+            labels = np.asarray(L["arc_label"], np.int32)
+            hyps.append([labels[paths[i][p]][labels[paths[i][p]] != 0] for p in range(K)])
+    else:
+        kept = [np.asarray(w, np.int32).reshape(-1) for w, ok in zip(one_bests, has_start) if ok]
+        hyps = [[w] * K for w in kept]
+    raw = compact_lattice_mbr_raw(csrs, points, hyps, do_mbr, workspace_limit)
+    for row in raw:
+        for r in row:
+            r["bayes_risk"] = np.float32(r["bayes_risk"])
+    it = iter(raw)
+    return [next(it) if ok else [None] * K for ok in has_start]
+
+
+def compact_lattice_mbr_last_timings():
+    """Milliseconds the last compact_lattice_mbr_raw call of this thread spent in host preparation (alpha and the arc
+    posteriors among it) / uploads / kernels / downloads, in the whole C call, in the host's part of MbrDecode, and the
+    number of kernel launches, rounds of the host loop, and AccStats() calls summed over the (lattice, point) pairs."""
+    ms = (C.c_float * 6)()
+    n = (C.c_int32 * 3)()
+    check(lib().kh_compact_lattice_mbr_last_timings(ms, n))
+    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], host_loop_ms=ms[5],
+                launches=n[0], rounds=n[1], acc_stats=n[2])
+
+
 def rescore_lattice(lats, loglikes, utt_row_offsets, tid2pdf=None):
     """RescoreLattice (lat/lattice-functions.cc:1307-1358) for a batch: loglikes = device
     matrix (rows of lattice i at utt_row_offsets[i]...).  Returns the new arc_acoustic arrays."""

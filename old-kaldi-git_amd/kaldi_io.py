@@ -414,6 +414,17 @@ def _write_object(f, binary, kind, obj):
         write_int32(f, binary, int(obj))
         if not binary:
             f.write(b"\n")
+    elif kind == "base_float_pair_vector":   # BasicPairVectorHolder<BaseFloat>::Write (kaldi-holder-inl.h:434-468)
+        pairs = np.asarray(obj, np.float32).reshape(-1, 2)
+        if binary:
+            write_int32(f, binary, len(pairs))
+        for i, (a, b) in enumerate(pairs):
+            write_float(f, binary, a)
+            write_float(f, binary, b)
+            if not binary and i + 1 < len(pairs):
+                f.write(b"; ")
+        if not binary:
+            f.write(b"\n")
     else:
         raise ValueError("unknown table object kind " + kind)
 

@@ -938,6 +938,16 @@ int kh_merge_pair_vector_summing(int64_t n, const int32_t *rows, const int32_t *
                                  int32_t n_rows, int32_t *out_rows, int32_t *out_keys, float *out_weights,
                                  int64_t *n_out);
 
+/* The device radix sort behind the (frame row, pdf) order of kh_discriminative_lattice_computations, by
+ * itself: HOST arrays of n (key, payload) pairs -> the pairs in the STABLE order of
+ *   (key & ((1 << lo_bits) - 1)) | (key & (((1 << hi_bits) - 1) << 32)),
+ * i.e. of the low lo_bits bits of the key's low word and the low hi_bits bits of its high word; the other
+ * key bits take no part in the order and are carried through unchanged.  0 <= n < 2^31 and
+ * 0 <= lo_bits, hi_bits <= 31 (a field of 0 bits takes no part), anything else is KH_EINVAL; n == 0
+ * succeeds and writes nothing.  Runs on the library's stream and returns when the outputs are written. */
+int kh_sort_pairs64(int64_t n, const uint64_t *keys, const int32_t *vals, int lo_bits, int hi_bits,
+                    uint64_t *keys_out, int32_t *vals_out);
+
 /* ------------------------------------------------------------------ f2
  * DeterminizeLatticePhonePrunedWrapper (lat/determinize-lattice-pruned.cc:1497-1519, called by
  * DecodeUtteranceLatticeFaster, decoder/decoder-wrappers.cc:264-274): the raw state-level

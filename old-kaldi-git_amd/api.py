@@ -2143,6 +2143,19 @@ def _merge_keyed(rows, cols, weights, n_rows=None):
     return orow[:m].astype(np.int64), ocol[:m].astype(np.int64), ow[:m]
 
 
+def sort_pairs64(keys, vals, lo_bits, hi_bits):
+    """kh_sort_pairs64: the device radix sort of the discriminative call by itself.  keys uint64 [n], vals int32 [n] (host)
+    -> (keys, vals) in the stable order of the keys' low lo_bits bits and the hi_bits bits from bit 32 on."""
+    k = np.ascontiguousarray(keys, np.uint64)
+    v = np.ascontiguousarray(vals, np.int32)
+    if k.ndim != 1 or k.shape != v.shape:
+        raise KhError("sort_pairs64: one payload per key")
+    ko, vo = np.empty_like(k), np.empty_like(v)
+    check(lib().kh_sort_pairs64(len(k), k.ctypes.data_as(capi.c_uint64_p), v.ctypes.data_as(capi.c_int32_p), int(lo_bits), int(hi_bits),
+                                ko.ctypes.data_as(capi.c_uint64_p), vo.ctypes.data_as(capi.c_int32_p)))
+    return ko, vo
+
+
 class DiscriminativeCall:
     """A discriminative_lattice_computations(..., begin=True) in flight: its device work is queued on a stream of its own
     (kh_discriminative_lattice_computations_begin); end() waits for it and returns what the plain call returns."""

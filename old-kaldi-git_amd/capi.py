@@ -237,6 +237,7 @@ SIGNATURES = {
     "kh_lattice_forward_backward_mpe": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, c_int32_p, C.c_int, C.c_int, c_float_p, c_double_p, c_int32_p]),
     "kh_rescore_lattice": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, vp, C.c_int, c_int32_p, vp]),
     "kh_merge_pair_vector_summing": (C.c_int, [i64, c_int32_p, c_int32_p, c_float_p, i32, c_int32_p, c_int32_p, c_float_p, c_int64_p]),
+    "kh_sort_pairs64": (C.c_int, [i64, c_uint64_p, c_int32_p, C.c_int, C.c_int, c_uint64_p, c_int32_p]),
     "kh_discriminative_lattice_computations": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p,
                                                         c_int32_p, c_int32_p, c_float_p, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int,
                                                         C.c_int, C.c_float, C.c_int, C.c_int, c_float_p, vp, KhMatrixDim, vp, KhMatrixDim, c_double_p]),

@@ -463,8 +463,12 @@ SortScatterKernel(const unsigned long long *__restrict__ kin, const int32_t *__r
   }
 }
 
+// Words of `work` that SortPairs64 needs for n pairs (one block of slack, as the discriminative call has always allocated).
+size_t SortWorkWords(int64_t n) { return static_cast<size_t>(kSortBins) * ((n + kSortTile - 1) / kSortTile + 1) + kSortBins; }
+
 // Sorts the n pairs (k0, v0) by the key bits [lo_bits) of the low word and [32, 32 + hi_bits) of the high word; the result is
 // in (k1, v1) (returned through *in_second = 1) or back in (k0, v0).  work: kSortBins * n_blocks + kSortBins words.
+// n < 2^31 (the cursors are 32-bit), 0 <= lo_bits, hi_bits <= 31; a half with 0 bits takes no part in the order.
 int SortPairs64(unsigned long long *k0, int32_t *v0, unsigned long long *k1, int32_t *v1, int64_t n, int lo_bits, int hi_bits,
                 uint32_t *work, hipStream_t st, int *in_second) {
   if (n <= 0) { *in_second = 0; return KH_OK; }   // nothing to sort: a 0-block launch is an error on HIP
@@ -492,6 +496,31 @@ int SortPairs64(unsigned long long *k0, int32_t *v0, unsigned long long *k1, int
 }
 
 }  // namespace
+
+// The device radix sort by itself, HOST arrays in and out (so that it can be checked against the definition of a stable
+// sort at sizes and bit fields the discriminative call does not reach in a test).
+extern "C" int kh_sort_pairs64(int64_t n, const uint64_t *keys, const int32_t *vals, int lo_bits, int hi_bits,
+                               uint64_t *keys_out, int32_t *vals_out) {
+  int rc = EnsureDevice();
+  if (rc) return rc;
+  KH_CHECK_ARG(n >= 0 && n < (1ll << 31) && lo_bits >= 0 && lo_bits <= 31 && hi_bits >= 0 && hi_bits <= 31 &&
+               (n == 0 || (keys && vals && keys_out && vals_out)));
+  if (n == 0) return KH_OK;
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the kernels' key type");
+  hipStream_t st = Stream();
+  DevArr<unsigned long long> d_k0, d_k1;
+  DevArr<int32_t> d_v0, d_v1;
+  DevArr<uint32_t> d_work;
+  if (d_k0.Alloc(n) || d_k1.Alloc(n) || d_v0.Alloc(n) || d_v1.Alloc(n) || d_work.Alloc(SortWorkWords(n))) return KH_ENOMEM;
+  KH_HIP(hipMemcpyAsync(d_k0.p, keys, sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
+  KH_HIP(hipMemcpyAsync(d_v0.p, vals, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+  int in_second = 0;
+  if ((rc = SortPairs64(d_k0.p, d_v0.p, d_k1.p, d_v1.p, n, lo_bits, hi_bits, d_work.p, st, &in_second))) return rc;
+  KH_HIP(hipMemcpyAsync(keys_out, in_second ? d_k1.p : d_k0.p, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+  KH_HIP(hipMemcpyAsync(vals_out, in_second ? d_v1.p : d_v0.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  KH_HIP(hipStreamSynchronize(st));
+  return KH_OK;
+}
 
 // Preparation shared by the lattice sweeps, ON THE DEVICE (one workgroup per lattice):
 // validation (top-sorted, consistent state times: LatticeStateTimes :36-67 and the
@@ -2235,7 +2264,7 @@ int DiscBegin(KhDiscCall &C,
   if (d_ali_pdf.Alloc(total_rows) || d_has_num.Alloc(total_rows) || d_vals.Alloc(A) || d_vals2.Alloc(A) || d_keys.Alloc(A) ||
       d_keys2.Alloc(A) || d_post.Alloc(A) || d_seg.Alloc(A) || d_tot.Alloc(n_lats) || d_ac.Alloc(n_lats) || d_num.Alloc(n_lats) ||
       d_part.Alloc(3 * kEmitBlocks) ||
-      d_sort.Alloc(static_cast<size_t>(kSortBins) * ((A + kSortTile - 1) / kSortTile + 1) + kSortBins))
+      d_sort.Alloc(SortWorkWords(A)))
     return KH_ENOMEM;
   // ---- beside the forward pass (side stream): the numerator's pdfs, the arcs' (row, pdf) keys and their stable sort;
   // arcs without a transition-id carry row = total_rows and end up last.  Only the bits that can be set take part: the

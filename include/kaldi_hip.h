@@ -267,7 +267,13 @@ int kh_diag_gmm_loglikes(const float *data, KhMatrixDim d_data,
  * LogLikelihoodZeroBased decodable-am-diag-gmm.cc:28-71 for every (t,pdf)):
  * out[t,j] = LogSumExp_{m in pdf j}(loglike[t,m], prune), LogSumExp as
  * matrix/kaldi-vector.cc:745-763.  All pdfs' Gaussians concatenated;
- * pdf_offsets: DEVICE int32 [num_pdfs+1]. */
+ * pdf_offsets: DEVICE int32 [num_pdfs+1], strictly increasing from 0 to
+ * num_mix (a DiagGmm has no empty mixture).  Every call copies them to the
+ * host, waits for the stream and checks that: KH_EINVAL with a message naming
+ * the pdf otherwise, before any kernel runs.  The call returns after its
+ * kernels have finished (it synchronises the stream again at its end).
+ * No frames (d_data.rows == 0): KH_EINVAL, "KALDI_ASSERT: data.NumRows() != 0"
+ * (diag-gmm.cc:548). */
 int kh_am_gmm_loglikes(const float *data, KhMatrixDim d_data,
                        const float *gconsts, const float *means_invvars,
                        const float *inv_vars, const int32_t *pdf_offsets,

@@ -681,6 +681,8 @@ class AmDiagGmm:
 
     def pdf_log_likelihoods(self, data, log_sum_exp_prune=-1.0, out=None):
         """frame x pdf matrix (gmm-compute-likes.cc:70-77)."""
+        if data.shape[0] == 0:
+            raise KhError("KALDI_ASSERT: data.NumRows() != 0")
         if data.shape[1] != self.dim:
             raise KhError("Dim mismatch: data dim = %d vs. model dim = %d" % (data.shape[1], self.dim))
         if out is None:

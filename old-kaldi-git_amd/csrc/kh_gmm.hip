@@ -16,8 +16,21 @@
 // Numerics per element (bit-identical to the CPU oracle):
 //   a1 = fmaf-chain_d(x_d, mi_d); a2 = fmaf-chain_d(x_d*x_d, iv_d);
 //   ll = (g + a1) + (-0.5f * a2)
-// Kernel 2: one thread per (frame, pdf): exact LogSumExp with the reference's
-// cutoff and double accumulation.
+// Kernel 2: one thread per (frame, pdf): LogSumExp with the reference's float cutoff, kept set
+// and double accumulation in Gaussian order.  The two transcendental steps are NOT libm's:
+// exp(x) is the hardware exp2 of the float product x * log2(e), log(sum) is the hardware log2
+// of the sum rounded to float, times ln 2 (ExpTerm / LogOfSum below).  Both units' accuracy is
+// taken as 1 ulp: the figure the "CDNA3 Instruction Set Architecture" guide gives for V_EXP_F32
+// and V_LOG_F32; gfx950 is assumed to match it.  Against the exact LogSumExp of the same float inputs the result is within
+//   1/2 ulp_f32(|result|) + c(n),   n = #Gaussians of the pdf,
+//   c(n) = 15.95 * 2^-24             rounding of the exp2 argument, |f - max| <= 15.95   9.5e-7
+//        + 2^-21 + 15.95 * 1.4e-8    float f - max; log2(e) as a float                   6.9e-7
+//        + 2^-23                     1 ulp of exp2                                       1.2e-7
+//        + 2^-24                     the sum rounded to float                            0.6e-7
+//        + ulp_f32(log2 n) * ln 2    1 ulp of log2                                  (n = 128: 3.3e-7)
+//        + ulp_f32(ln n)             the product with ln 2 (as a float), rounded    (n = 128: 4.8e-7)
+// = 2.6e-6 for a pdf of 128 Gaussians (tests/gmm_cases.py derives it and the suite holds the
+// kernels to twice that); the project's requirement on frame log-likelihoods is 1e-4.
 #include <cfloat>
 #include <cmath>
 #include <vector>
@@ -84,9 +97,10 @@ GmmLoglikesKernel(const float *__restrict__ data, int T, int D, int data_stride,
 
 // The two transcendental steps of LogSumExp (kaldi-vector.cc:755-761: "sum += Exp(f - max)",
 // "max + Log(sum)") on the hardware's exp2 / log2 units: exp(x) = exp2(x * log2 e) and
-// log(s) = log2(s) * ln 2, each within ~2 ulp of a float.  The terms lie in (0, 1], the double
-// sum in [1, #Gaussians of the pdf]; against the 4e-6 ulp of the float result (|score| ~ 50)
-// the error is < 1e-6 - north_star asks 1e-4 on frame log-likelihoods.  The libm versions
+// log(s) = log2(s) * ln 2.  The terms lie in (0, 1], the double sum in [1, #Gaussians of the pdf].
+// The error against the exact LogSumExp is derived in this file's header: c(n) = 2.6e-6 for a pdf
+// of 128 Gaussians beside the 1/2 ulp (2e-6 at |score| ~ 50) of the float result - north_star asks
+// 1e-4 on frame log-likelihoods.  The libm versions
 // (expf: ~15 VALU instructions, double log: ~150) made the fused kernel VALU-bound: 38 VALU
 // instructions per MFMA instruction, matrix pipe 18 % busy.
 __device__ __forceinline__ float ExpTerm(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
@@ -180,7 +194,7 @@ int LaunchLoglikes(const float *data, KhMatrixDim dd, const float *g,
 // Per tile: means_invvars / inv_vars / gconsts of the tile -> LDS ([k][gaussian] image,
 // conflict-free ds_read_b32 fragments), two v_mfma_f32_32x32x2_f32 accumulations
 // (k-ordered fmaf chains, as the unfused path), ll = (a1 + g) + (-0.5 a2) -> LDS
-// [frame][gaussian], then one lane per (frame, pdf): max, cutoff, double sum of expf, log.
+// [frame][gaussian], then one lane per (frame, pdf): max, cutoff, double sum of ExpTerm, LogOfSum.
 // Same operations in the same order as kh_diag_gmm_loglikes + GmmPdfLseRowKernel: the
 // results are bit-identical to the unfused path.
 // Measured (200 k frames, cfg 2): 5.0 ms.  History: 6.2 ms = matrix cores 2.2 ms (their floor: 2 x 200k x
@@ -507,16 +521,34 @@ int kh_am_gmm_loglikes(const float *data, KhMatrixDim dd, const float *gconsts,
   int rc = EnsureDevice();
   if (rc) return rc;
   KH_CHECK_ARG(pdf_offsets && out && num_pdfs > 0 && out_stride >= num_pdfs);
+  KH_CHECK_ARG(data && gconsts && means_invvars && inv_vars && dd.cols > 0 && dd.stride >= dd.cols && num_mix > 0);
+  if (dd.rows <= 0) {  // DiagGmm::LogLikelihoods, diag-gmm.cc:548
+    SetError("KALDI_ASSERT: data.NumRows() != 0");
+    return KH_EINVAL;
+  }
   const float min_log_diff_f = logf(FLT_EPSILON);  // kMinLogDiffFloat kaldi-math.h:121
+  // The pdfs' Gaussian ranges: strictly increasing from 0 to num_mix (a DiagGmm has no empty mixture).  Both
+  // paths below index with them unchecked - the fused kernel's boundary array holds kGT + 1 entries per tile.
+  std::vector<int32_t> h_off(num_pdfs + 1);
+  KH_HIP(hipMemcpyAsync(h_off.data(), pdf_offsets, sizeof(int32_t) * (num_pdfs + 1), hipMemcpyDeviceToHost, Stream()));
+  KH_HIP(hipStreamSynchronize(Stream()));
+  if (h_off[0] != 0) {
+    SetError("kh_am_gmm_loglikes: pdf_offsets[0] = %d: pdf 0 does not start at Gaussian 0", h_off[0]);
+    return KH_EINVAL;
+  }
+  for (int j = 0; j < num_pdfs; j++)
+    if (h_off[j + 1] <= h_off[j]) {
+      SetError("kh_am_gmm_loglikes: pdf %d is empty or runs backwards (pdf_offsets %d .. %d)", j, h_off[j], h_off[j + 1]);
+      return KH_EINVAL;
+    }
+  if (h_off[num_pdfs] != num_mix) {
+    SetError("kh_am_gmm_loglikes: pdf %d ends at Gaussian %d, the model has %d", num_pdfs - 1, h_off[num_pdfs], num_mix);
+    return KH_EINVAL;
+  }
   // Fused path (matrix cores + LogSumExp epilogue, nothing of T x #Gaussians in HBM) whenever
   // the problem is large enough for the tiles to fill the chip and every pdf fits a tile.
   if (dd.cols <= 40 && static_cast<int64_t>(dd.rows) * num_mix >= (1 << 22) && !getenv("KH_GMM_NO_FUSION") &&
       !getenv("KH_GMM_NO_GEMM")) {
-    KH_CHECK_ARG(data && gconsts && means_invvars && inv_vars && dd.rows > 0 && dd.cols > 0 && dd.stride >= dd.cols);
-    std::vector<int32_t> h_off(num_pdfs + 1);
-    KH_HIP(hipMemcpyAsync(h_off.data(), pdf_offsets, sizeof(int32_t) * (num_pdfs + 1), hipMemcpyDeviceToHost, Stream()));
-    KH_HIP(hipStreamSynchronize(Stream()));
-    KH_CHECK_ARG(h_off[0] == 0 && h_off[num_pdfs] == num_mix);
     std::vector<GmmTile> tiles;
     if (BuildGmmTiles(h_off, &tiles)) {
       GmmTile *d_tiles = static_cast<GmmTile *>(PoolMalloc(sizeof(GmmTile) * tiles.size()));

@@ -247,7 +247,8 @@ def test_gmm_fused_logsumexp_equals_unfused(api, monkeypatch):
     rng = np.random.default_rng(99)
     for (n_pdf, n_gauss, dim, T) in ((1800, 9000, 39, 731), (700, 6000, 13, 1000)):
         am = workloads.make_am_gmm(rng, n_pdf, n_gauss, dim)
-        # a few large pdfs (up to 100 Gaussians) among the small ones: tiles of whole pdfs
+        # mixture counts jittered by +-2 round the average (5 and 8.6: the largest pdf has 14 Gaussians): tiles of many
+        # whole small pdfs; pdfs of up to 128 Gaussians and a tile of one pdf are test_gpu_gmm_dispatch.py's
         mi, iv = workloads.gmm_inv_params(am)
         g, _ = api.gmm_compute_gconsts(am["weights"], mi, iv)
         gmm = api.AmDiagGmm(g, mi, iv, am["pdf_offsets"])

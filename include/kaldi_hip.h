@@ -844,6 +844,83 @@ int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offsets, const i
 int kh_compact_lattice_mbr_set_workspace_limit(size_t bytes);
 int kh_compact_lattice_mbr_last_timings(float *ms6, int32_t *counts3);
 
+/* WordAlignLattice (lat/word-align-lattice.{h,cc}, class LatticeWordAligner; latbin/lattice-align-words.cc) for a batch of
+ * top-sorted CompactLattices in one call (csrc/kh_latalign.hip).  HOST CSR as kh_compact_lattice_prune takes it (every arc
+ * to a higher-numbered state; lat_start < 0 or no states = an empty lattice), with the transition-id strings: arc a's at
+ * arc_strings[arc_string_offsets[a] .. [a + 1]), state s's final string at final_strings[final_string_offsets[s] .. [s + 1]).
+ * tid_phone / tid_is_final / tid_is_self_loop: TransitionIdToPhone, IsFinal, IsSelfLoop as arrays of num_tids + 1 entries
+ * indexed by transition-id; phone_type[p], n_phone_types entries: WordBoundaryInfo::phone_to_type (0 kNoPhone, 1 begin,
+ * 2 end, 3 singleton, 4 internal, 5 nonword); reorder, silence_label, partial_word_label: its other members; max_states[l]
+ * (NULL = all 0): WordAlignLattice's argument.
+ *
+ * THE RESULT.  The reference explores tuples (input state, pending transition-ids, pending words) of the input after
+ * fst::CreateSuperFinal (fstext/fstext-utils-inl.h: a single final state with weight One, an empty string and no arcs is
+ * used as it is; otherwise a new highest-numbered state becomes the only final state and every old final state gets a
+ * label-0 arc to it that carries its whole final weight, string included), with 0 silence / partial-word labels replaced by
+ * 1 + the highest label of the lattice (:275-282).  ProcessQueueElement (:201-250) either cuts a word, silence or one-phone
+ * word off the front of the pending ids (OutputArc :59-69, a labelled arc) or emits one epsilon arc per input arc (Advance
+ * :40-48, which carries the arc's weight) and, on the final state, ProcessFinal (:172-198) with OutputArcForce (:554-635);
+ * RmEpsilon(connect) follows, whose state numbering and arc order are OpenFst's and are not reproduced.  What the problem
+ * fixes is reproduced: every stored tuple has weight One, so tuple identity is (input state, pending ids, pending words).
+ *   Output states: the start tuple (start, -, -) and every destination of a labelled arc, if a final weight is reachable.
+ *   Arcs of an output state S: over every tuple T reachable from S by Advance alone (a tuple whose OutputArc succeeds takes
+ *   no epsilon step, :214), d(S, T) = the Times of the input arcs' weights along the path, two float sums accumulated left
+ *   to right from One; a T whose OutputArc succeeds gives the arc S -> T' with that label, string and weight d(S, T); a T on
+ *   the final state with something pending gives the arc of OutputArcForce in the same way - the label-0, empty-string arc
+ *   of :574-589 that discards word labels included, as an arc -; a T on the final state with nothing pending Plus-es
+ *   d(S, T) into S's final weight.  Where two epsilon paths reach the same T (input that is not deterministic), d(S, T) is
+ *   their Plus, taken before T is expanded (tuples in ascending input state).  Two arcs of S with the same destination and
+ *   label (before the temporary labels are mapped back to 0) are merged by Plus of CompactLatticeWeight
+ *   (fstext/lattice-weight.h:562-608: the better weight with its string; where Compare of two LatticeWeights is 0 and the
+ *   acoustic costs still differ, the smaller acoustic cost is the better one here, so Plus does not depend on order).
+ *   Times: every path to an input state reachable from the start must consume the same number of transition-ids, else
+ *   KH_EINVAL with the state named (a deliberate difference: the reference goes on).  time(S) = time(input state) - number
+ *   of pending ids.
+ *   NUMBERING (this library's rule): the start state is state 0; the others ascend by the key (time(S), input state,
+ *   descending number of pending words, pending words lexicographically, pending ids lexicographically) - a topological
+ *   order, since a labelled arc consumes at least one id, except the discarding arc above, which stays on its input state
+ *   and goes from k > 0 pending words to none.  A state's arcs ascend by (destination, label).
+ *   status[l]: KH_ALIGN_OK; KH_ALIGN_ERROR = aligned, and one of the conditions that set error_ held at some tuple
+ *   (:361-365, :420-425, :464-469, :478-483, :494-498, :508-513, :565-568, :578-582, :604-613, :621-624; :375-379 and
+ *   :406-410 only warn) - an OR, so independent of the order of visits; KH_ALIGN_EMPTY = no start state;
+ *   KH_ALIGN_TOO_MANY_STATES = max_states > 0 and the construction holds more than max_states distinct tuples (the lattices
+ *   for which :315 fires), no lattice returned - the reference returns the fragment its LIFO order had reached;
+ *   KH_ALIGN_FATAL = the KALDI_ERR of :595-603 at some tuple, whichever other condition held, no lattice returned (too
+ *   many states is reported before it).  n_tuples[l] = distinct tuples explored; max_states + 1 for
+ *   KH_ALIGN_TOO_MANY_STATES (the construction stops at the tuple that pushes the count over), 0 for KH_ALIGN_EMPTY.
+ * Outputs (HOST): per lattice status, n_states, n_arcs, n_tuples, n_string_words - always written; the three out_*_offsets
+ * arrays (n_lats + 1 entries) are the room the caller leaves, and KH_EINVAL is returned, nothing else written, when a
+ * lattice does not fit, so a second call with the room they name succeeds.  Lattice l's states at out_state_offsets[l]:
+ * final weights (+inf, +inf = not final; final strings are empty); its arcs at out_arc_offsets[l], sorted by source state:
+ * source, destination, label, graph and acoustic cost, string length; the strings one after the other in arc order at
+ * out_string_offsets[l].  A status without a lattice has 0 states.
+ * The construction runs on the device, one wave per lattice; the sort and the merges on the host.  Workspace per lattice in
+ * flight: tables for 4 (states + arcs) + 64 tuples and twice as many (S, T) pairs, an arena of 4 x the lattice's
+ * transition-ids + 16 (states + arcs) words; a lattice whose tables run full is run again with twice the room.  Lattices are taken largest first, as
+ * many per launch as half of the free device memory admits, or as kh_compact_lattice_align_words_set_workspace_limit(bytes)
+ * admits: a setting of the CALLING THREAD (0 = back to automatic; one lattice always runs).
+ * kh_compact_lattice_align_words_last_timings: milliseconds the last call of this thread spent in { host preparation,
+ * uploads, kernels with their memsets, downloads (HIP events), the whole call by the host's clock, the host's sort and
+ * merge }, and counts3 (may be NULL) = { kernel launches, lattices run again with more room, tuples over all lattices }. */
+#define KH_ALIGN_OK 0
+#define KH_ALIGN_ERROR 1
+#define KH_ALIGN_EMPTY 2
+#define KH_ALIGN_TOO_MANY_STATES 3
+#define KH_ALIGN_FATAL 4
+int kh_compact_lattice_align_words(
+    int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start, const int64_t *arc_offsets,
+    const int32_t *arc_label, const int32_t *arc_nextstate, const float *arc_graph, const float *arc_acoustic,
+    const int64_t *arc_string_offsets, const int32_t *arc_strings, const float *final_graph, const float *final_acoustic,
+    const int64_t *final_string_offsets, const int32_t *final_strings, int num_tids, const int32_t *tid_phone,
+    const int32_t *tid_is_final, const int32_t *tid_is_self_loop, int n_phone_types, const int32_t *phone_type, int reorder,
+    int silence_label, int partial_word_label, const int32_t *max_states, int32_t *status, int32_t *n_states,
+    int32_t *n_arcs, int32_t *n_tuples, int64_t *n_string_words, const int64_t *out_state_offsets,
+    const int64_t *out_arc_offsets, const int64_t *out_string_offsets, float *out_final_graph, float *out_final_acoustic,
+    int32_t *out_arc_src, int32_t *out_arc_nextstate, int32_t *out_arc_label, float *out_arc_graph, float *out_arc_acoustic,
+    int32_t *out_arc_string_len, int32_t *out_strings);
+int kh_compact_lattice_align_words_set_workspace_limit(size_t bytes);
+int kh_compact_lattice_align_words_last_timings(float *ms6, int32_t *counts3);
+
 /* LatticeForwardBackwardMpeVariants (lat/lattice-functions.cc:740-919): criterion
  * "smbr" (is_mpfe = 0) or "mpfe".  tid2phone / tid2pdf = TransitionIdToPhone /
  * TransitionIdToPdf as arrays of num_tids + 1 entries indexed by transition-id;

@@ -2017,6 +2017,160 @@ def compact_lattice_mbr_last_timings():
                 launches=n[0], rounds=n[1], acc_stats=n[2])
 
 
+ALIGN_OK, ALIGN_ERROR, ALIGN_EMPTY, ALIGN_TOO_MANY_STATES, ALIGN_FATAL = range(5)
+
+
+def compact_lattice_align_csr(clat):
+    """CompactLattice dict (kaldi_io.read_compact_lattice, with the strings) -> the top-sorted CSR dict of
+    compact_lattice_to_csr plus start, arc_string and final_string (lists of int32 arrays in CSR order)."""
+    n = int(clat["n_states"])
+    start = int(clat.get("start", 0))
+    if n == 0 or start < 0:
+        return dict(n_states=0, start=-1, arc_offsets=np.zeros(1, np.int64), arc_label=np.zeros(0, np.int32),
+                    arc_nextstate=np.zeros(0, np.int32), arc_graph=np.zeros(0, np.float32), arc_acoustic=np.zeros(0, np.float32),
+                    final_graph=np.zeros(0, np.float32), final_acoustic=np.zeros(0, np.float32), arc_string=[], final_string=[])
+    order = compact_lattice_top_order(clat)
+    L = compact_lattice_to_csr(clat)
+    L["start"] = start if order is None else int(order[start])
+    L["arc_string"] = [np.asarray(clat["arc_string"][j], np.int32).reshape(-1) for j in L["perm"]]
+    L["final_string"] = [np.asarray(clat["final_string"][s], np.int32).reshape(-1) for s in L["state_of"]]
+    return L
+
+
+def compact_lattice_align_words_pack(csrs, tmodel, wbinfo, max_states=0):
+    """The arguments of kh_compact_lattice_align_words as contiguous arrays: a dict in the C call's order of names."""
+    n = len(csrs)
+    soff = np.zeros(n + 1, np.int32)
+    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
+    aoff, base = [np.zeros(1, np.int64)], 0
+    for L in csrs:
+        o = np.asarray(L["arc_offsets"], np.int64)
+        aoff.append(o[1:] + base)
+        base += int(o[-1])
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt).reshape(-1) for L in csrs] + [np.zeros(0, dt)]))
+    arc_strings = [x for L in csrs for x in L["arc_string"]]
+    final_strings = [x for L in csrs for x in L["final_string"]]
+    offs = lambda strs: np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(x) for x in strs])]).astype(np.int64))
+    flat = lambda strs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in strs] + [np.zeros(0, np.int32)]))
+    i32 = lambda x: np.ascontiguousarray(np.asarray(x).astype(np.int32).reshape(-1))
+    ms = np.broadcast_to(np.asarray(max_states, np.int64), (n,)) if np.ndim(max_states) == 0 else np.asarray(max_states, np.int64)
+    if np.any(ms < 0) or np.any(ms >= 2 ** 31):
+        raise KhError("compact_lattice_align_words: max_states out of range")
+    return dict(lat_state_offsets=soff, lat_start=i32([int(L.get("start", 0)) for L in csrs]),
+                arc_offsets=np.ascontiguousarray(np.concatenate(aoff)), arc_label=cat("arc_label", np.int32),
+                arc_nextstate=cat("arc_nextstate", np.int32), arc_graph=cat("arc_graph", np.float32),
+                arc_acoustic=cat("arc_acoustic", np.float32), arc_string_offsets=offs(arc_strings), arc_strings=flat(arc_strings),
+                final_graph=cat("final_graph", np.float32), final_acoustic=cat("final_acoustic", np.float32),
+                final_string_offsets=offs(final_strings), final_strings=flat(final_strings),
+                tid_phone=i32(tmodel["tid2phone"]), tid_is_final=i32(tmodel["tid_is_final"]),
+                tid_is_self_loop=i32(tmodel["tid_is_self_loop"]), phone_type=i32(wbinfo["phone_to_type"]),
+                reorder=int(bool(wbinfo["reorder"])), silence_label=int(wbinfo["silence_label"]),
+                partial_word_label=int(wbinfo["partial_word_label"]), max_states=i32(ms))
+
+
+def compact_lattice_align_words_call(A, room_s, room_a, room_w, fill=0):
+    """One kh_compact_lattice_align_words call on compact_lattice_align_words_pack's arrays with the given room per lattice
+    (states, arcs, transition-ids).  Returns (rc, counts, outputs): counts = dict(status, n_states, n_arcs, n_tuples,
+    n_string_words), outputs = dict of the offset arrays and the output arrays, created filled with `fill`."""
+    n = len(A["lat_start"])
+    status, ns, na, nt = (np.zeros(n, np.int32) for _ in range(4))
+    nw = np.zeros(n, np.int64)
+    offs = lambda r: np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.asarray(r, np.int64).reshape(n))]).astype(np.int64))
+    so, ao, wo = offs(room_s), offs(room_a), offs(room_w)
+    f32 = lambda k: np.full(int(k), fill, np.float32)
+    i32 = lambda k: np.full(int(k), fill, np.int32)
+    O = dict(state_offsets=so, arc_offsets=ao, string_offsets=wo, final_graph=f32(so[-1]), final_acoustic=f32(so[-1]),
+             arc_src=i32(ao[-1]), arc_nextstate=i32(ao[-1]), arc_label=i32(ao[-1]), arc_graph=f32(ao[-1]), arc_acoustic=f32(ao[-1]),
+             arc_string_len=i32(ao[-1]), strings=i32(wo[-1]))
+    ip, fp, lp = capi.c_int32_p, capi.c_float_p, capi.c_int64_p
+    ptr = lambda x, t: x.ctypes.data_as(t)
+    rc = lib().kh_compact_lattice_align_words(
+        n, ptr(A["lat_state_offsets"], ip), ptr(A["lat_start"], ip), ptr(A["arc_offsets"], lp), ptr(A["arc_label"], ip),
+        ptr(A["arc_nextstate"], ip), ptr(A["arc_graph"], fp), ptr(A["arc_acoustic"], fp), ptr(A["arc_string_offsets"], lp),
+        ptr(A["arc_strings"], ip), ptr(A["final_graph"], fp), ptr(A["final_acoustic"], fp), ptr(A["final_string_offsets"], lp),
+        ptr(A["final_strings"], ip), len(A["tid_phone"]) - 1, ptr(A["tid_phone"], ip), ptr(A["tid_is_final"], ip),
+        ptr(A["tid_is_self_loop"], ip), len(A["phone_type"]), ptr(A["phone_type"], ip), A["reorder"], A["silence_label"],
+        A["partial_word_label"], ptr(A["max_states"], ip), ptr(status, ip), ptr(ns, ip), ptr(na, ip), ptr(nt, ip), ptr(nw, lp),
+        ptr(so, lp), ptr(ao, lp), ptr(wo, lp), ptr(O["final_graph"], fp), ptr(O["final_acoustic"], fp), ptr(O["arc_src"], ip),
+        ptr(O["arc_nextstate"], ip), ptr(O["arc_label"], ip), ptr(O["arc_graph"], fp), ptr(O["arc_acoustic"], fp),
+        ptr(O["arc_string_len"], ip), ptr(O["strings"], ip))
+    return rc, dict(status=status, n_states=ns, n_arcs=na, n_tuples=nt, n_string_words=nw), O
+
+
+def compact_lattice_align_words_raw(csrs, tmodel, wbinfo, max_states=0, workspace_limit=None, room=None):
+    """kh_compact_lattice_align_words on CSR dicts (compact_lattice_align_csr).  Returns per lattice dict(status, n_tuples,
+    n_states, final [n x 2 float32], arcs [(src, dst, label, g, a, string)]).  room: None = a guess from the input, run once
+    more with the room the first call's counts name when they exceed it; or (states, arcs, transition-ids) per lattice, taken
+    as it is."""
+    n = len(csrs)
+    if n == 0:
+        raise KhError("compact_lattice_align_words: no lattices")
+    A = compact_lattice_align_words_pack(csrs, tmodel, wbinfo, max_states)
+    if len(A["tid_phone"]) != len(A["tid_is_final"]) or len(A["tid_phone"]) != len(A["tid_is_self_loop"]) or len(A["tid_phone"]) < 2:
+        raise KhError("compact_lattice_align_words: the three transition-id tables differ in length")
+    if room is None:
+        words = np.asarray([sum(len(x) for x in L["arc_string"]) + sum(len(x) for x in L["final_string"]) for L in csrs], np.int64)
+        arcs = np.diff(A["lat_state_offsets"]).astype(np.int64) + np.asarray([int(L["arc_offsets"][-1]) for L in csrs], np.int64)
+        rooms = [2 * arcs + 4, 2 * arcs + 4, 2 * words + 4]
+    else:
+        rooms = [np.asarray(r, np.int64).reshape(n) for r in room]
+    if workspace_limit is not None:
+        check(lib().kh_compact_lattice_align_words_set_workspace_limit(int(workspace_limit)))
+    try:
+        rc, cnt, O = compact_lattice_align_words_call(A, *rooms)
+        need = [cnt["n_states"].astype(np.int64), cnt["n_arcs"].astype(np.int64), cnt["n_string_words"].astype(np.int64)]
+        if rc != 0 and room is None and any(np.any(x > r) for x, r in zip(need, rooms)):   # the counts are always written
+            rc, cnt, O = compact_lattice_align_words_call(A, *need)
+        check(rc)
+    finally:
+        if workspace_limit is not None:
+            check(lib().kh_compact_lattice_align_words_set_workspace_limit(0))
+    so, ao, wo, alen, strs = O["state_offsets"], O["arc_offsets"], O["string_offsets"], O["arc_string_len"], O["strings"]
+    out = []
+    for i in range(n):
+        s0, a0, w0, ns, na = int(so[i]), int(ao[i]), int(wo[i]), int(cnt["n_states"][i]), int(cnt["n_arcs"][i])
+        ends = w0 + np.cumsum(alen[a0:a0 + na])
+        arcs = [(int(O["arc_src"][a0 + k]), int(O["arc_nextstate"][a0 + k]), int(O["arc_label"][a0 + k]), O["arc_graph"][a0 + k],
+                 O["arc_acoustic"][a0 + k], tuple(strs[int(ends[k]) - int(alen[a0 + k]):int(ends[k])].tolist())) for k in range(na)]
+        out.append(dict(status=int(cnt["status"][i]), n_tuples=int(cnt["n_tuples"][i]), n_states=ns,
+                        final=np.stack([O["final_graph"][s0:s0 + ns], O["final_acoustic"][s0:s0 + ns]], axis=1), arcs=arcs))
+    return out
+
+
+def compact_lattice_align_words(clats, tmodel, wbinfo, max_states=0, workspace_limit=None):
+    """WordAlignLattice (lat/word-align-lattice.cc; lattice-align-words) for a batch of CompactLattices (dicts of
+    kaldi_io.read_compact_lattice, with the strings) in ONE call.  tmodel: kaldi_io.read_transition_model's dict (tid2phone,
+    tid_is_final, tid_is_self_loop); wbinfo: kaldi_io.read_word_boundary_info's; max_states: one number or one per lattice
+    (0 = no limit).  Returns per lattice dict(status [ALIGN_*], n_tuples, clat): clat the aligned lattice in the same dict
+    layout, numbered by the rule of include/kaldi_hip.h (top-sorted, start state 0), or None where there is none (empty
+    input, too many states, fatal, or no path left).  A lattice that is not top-sorted is renumbered by
+    compact_lattice_top_order first."""
+    raw = compact_lattice_align_words_raw([compact_lattice_align_csr(c) for c in clats], tmodel, wbinfo, max_states, workspace_limit)
+    out = []
+    for r in raw:
+        c = None
+        if r["n_states"] > 0:
+            arcs, m = r["arcs"], r["n_states"]
+            c = dict(n_states=m, start=0, arc_src=np.asarray([x[0] for x in arcs], np.int32),
+                     arc_dst=np.asarray([x[1] for x in arcs], np.int32), arc_label=np.asarray([x[2] for x in arcs], np.int32),
+                     arc_g=np.asarray([x[3] for x in arcs], np.float32), arc_a=np.asarray([x[4] for x in arcs], np.float32),
+                     arc_string=[np.asarray(x[5], np.int32) for x in arcs], final_g=r["final"][:, 0].copy(),
+                     final_a=r["final"][:, 1].copy(), final_string=[np.zeros(0, np.int32) for _ in range(m)])
+        out.append(dict(status=r["status"], n_tuples=r["n_tuples"], clat=c))
+    return out
+
+
+def compact_lattice_align_words_last_timings():
+    """Milliseconds the last compact_lattice_align_words_raw call of this thread spent in host preparation / uploads / kernels
+    / downloads, in the whole C call, in the host's sort and merge, and the number of kernel launches, of lattices run again
+    with more room, and of tuples over all lattices."""
+    ms = (C.c_float * 6)()
+    n = (C.c_int32 * 3)()
+    check(lib().kh_compact_lattice_align_words_last_timings(ms, n))
+    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], host_finish_ms=ms[5],
+                launches=n[0], run_again=n[1], tuples=n[2])
+
+
 def rescore_lattice(lats, loglikes, utt_row_offsets, tid2pdf=None):
     """RescoreLattice (lat/lattice-functions.cc:1307-1358) for a batch: loglikes = device
     matrix (rows of lattice i at utt_row_offsets[i]...).  Returns the new arc_acoustic arrays."""

@@ -808,7 +808,7 @@ def read_transition_model(s, binary):
     expect_token(s, binary, "</LogProbs>")
     expect_token(s, binary, "</TransitionModel>")
     # ComputeDerived :72-98: transition-ids are numbered triple by triple, transition by transition of the HMM-state's topology entry
-    tid2pdf, tid2phone, tid2hmm, tid_self = [-1], [0], [-1], [False]
+    tid2pdf, tid2phone, tid2hmm, tid_self, tid_final = [-1], [0], [-1], [False], [False]
     for phone, hmm_state, pdf in triples:
         entry = topo["entries"][topo["phone2idx"][phone]]
         trans = entry[hmm_state][1]
@@ -816,11 +816,51 @@ def read_transition_model(s, binary):
         tid2phone += [int(phone)] * len(trans)                       # TransitionIdToPhone :235-239
         tid2hmm += [int(hmm_state)] * len(trans)                     # TransitionIdToHmmState :247-251
         tid_self += [int(dst) == int(hmm_state) for dst, _ in trans]  # IsSelfLoop :217-225
+        tid_final += [int(dst) == len(entry) - 1 for dst, _ in trans]  # IsFinal :200-215: into the entry's last state
     if len(tid2pdf) != len(log_probs):
         raise ValueError("TransitionModel: %d transition-ids but %d log-probs" % (len(tid2pdf) - 1, len(log_probs)))
     return dict(topo=topo, triples=triples, log_probs=log_probs.astype(np.float32), tid2pdf=np.asarray(tid2pdf, np.int32),
                 tid2phone=np.asarray(tid2phone, np.int32), tid2hmm_state=np.asarray(tid2hmm, np.int32),
-                tid_is_self_loop=np.asarray(tid_self, bool))
+                tid_is_self_loop=np.asarray(tid_self, bool), tid_is_final=np.asarray(tid_final, bool))
+
+
+WORD_BOUNDARY_TYPES = {"begin": 1, "end": 2, "singleton": 3, "internal": 4, "nonword": 5}   # WordBoundaryInfo::PhoneType
+
+
+def read_word_boundary_info(path, reorder=True, silence_label=0, partial_word_label=0):
+    """WordBoundaryInfo(opts, word_boundary_file) with Init (lat/word-align-lattice.cc:675-709): a text file of lines
+    "<phone> begin|end|singleton|internal|nonword".  Returns dict(phone_to_type [int32, 0 = kNoPhone], reorder,
+    silence_label, partial_word_label); the defaults are WordBoundaryInfoNewOpts'."""
+    with open(path, "rb") as f:
+        data = f.read()
+    return parse_word_boundary_info(data, reorder, silence_label, partial_word_label)
+
+
+def parse_word_boundary_info(data, reorder=True, silence_label=0, partial_word_label=0):
+    """read_word_boundary_info on the file's bytes (for a word-boundary rxfilename that is a pipe or standard input)."""
+    if data[:2] == b"\0B":
+        raise ValueError("Not expecting binary word-boundary file.")
+    types = []
+    lines = data.decode().split("\n")
+    if lines[-1] == "":          # std::getline: no line behind the last newline
+        lines.pop()
+    for line in lines:
+        parts = [w for w in line.replace("\t", " ").replace("\r", " ").split(" ") if w]
+        try:
+            p = int(parts[0]) if len(parts) == 2 else None
+        except ValueError:
+            p = None
+        if p is None or not -2 ** 31 <= p < 2 ** 31 or parts[1] not in WORD_BOUNDARY_TYPES:
+            raise ValueError("Invalid line in word-boundary file: " + line)
+        if p <= 0:
+            raise ValueError("word-boundary file: phone ids are positive: " + line)
+        if len(types) <= p:
+            types += [0] * (p + 1 - len(types))
+        types[p] = WORD_BOUNDARY_TYPES[parts[1]]
+    if not types:
+        raise ValueError("Empty word-boundary file")
+    return dict(phone_to_type=np.asarray(types, np.int32), reorder=bool(reorder), silence_label=int(silence_label),
+                partial_word_label=int(partial_word_label))
 
 
 def read_diag_gmm(s, binary):

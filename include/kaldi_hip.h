@@ -921,6 +921,73 @@ int kh_compact_lattice_align_words(
 int kh_compact_lattice_align_words_set_workspace_limit(size_t bytes);
 int kh_compact_lattice_align_words_last_timings(float *ms6, int32_t *counts3);
 
+/* Forced alignment of a batch of utterances, each against its own graph: FasterDecoder (decoder/faster-decoder.{h,cc}) as
+ * AlignUtteranceWrapper drives it (decoder/decoder-wrappers.cc:456-482; gmm-align-compiled, nnet-align-compiled), with
+ * max_active = INT_MAX.  One call = one Decode() per utterance with the given beam; the retry with a second beam is the
+ * caller's second call over the utterances that came back KH_ALIGNC_NO_FINAL.
+ *   Graphs: concatenated in the CSR layout of kaldi_io.read_fst.  state_offsets (n_utts + 1): the first state of every
+ *   utterance; arc_offsets (all states + 1, int64): the arcs of every state, numbered over the batch; start, nextstate:
+ *   state numbers inside the utterance; final_w: +inf = not final.  tid2pdf: HOST table of n_tid entries indexed by
+ *   transition-id (NULL = ilabel - 1); every ilabel is 0 or in 1..n_tid-1.
+ *   loglikes: DEVICE matrix of ll_rows x ll_cols floats with ll_stride, as for kh_decoder_decode: row t of utterance u at
+ *   utt_row_offsets[u] + t (host, n_utts + 1), column tid2pdf[ilabel]; ac_cost = -loglikes.
+ * Reproduced with the reference's own arithmetic: token costs are doubles formed as (prev + float arc weight) + float
+ * ac_cost (faster-decoder.h:115-132); GetCutoff (:151-213) with its min_active branch, which takes the (min_active+1)-th
+ * smallest cost AFTER rounding each to float (tmp_array_ is a vector<BaseFloat>), gives +inf for cutoff and adaptive beam
+ * at <= min_active tokens, and forms adaptive_beam = float(min_active_cutoff - best + beam_delta); ProcessNonemitting
+ * (:306-346) accepts at <= cutoff and a strictly better cost replaces; the initial closure of InitDecoding (:36-45);
+ * ReachedFinal and the best final token (:78-112).
+ * THE ONE DELIBERATE DIFFERENCE: ProcessEmitting (:263-300) accepts a candidate against next_weight_cutoff while that value
+ * still tightens as the HashList is walked, so which marginal tokens exist depends on the list's order.  This library
+ * accepts against the frame's FINAL value, min over all candidates from propagating tokens of (new_weight + adaptive_beam),
+ * which does not depend on any order.  Every token the reference has and this library lacks is at least adaptive_beam worse
+ * than the frame's best; it can matter only through the min_active count of the next frame or by a comeback.  The list's
+ * order is not reproduced.
+ * TIES: the reference gives equal costs to the first arrival in list order; this library to the lowest arc position in the
+ * utterance's CSR among the candidates of one pass (an emitting arc is only replaced by a STRICTLY better eps arc; the eps
+ * closure runs in rounds, each round relaxing every state from the costs of the round before), and among final tokens of
+ * equal total cost to the lowest state.  The path is read from per-(frame, state) backpointers; where the reference's token
+ * keeps pointing at a predecessor token that was later replaced by a better one whose cost rounds to the same sum, the
+ * library's path goes through the replacement.
+ * Output per utterance u, path room path_offsets[u+1] - path_offsets[u] (n_utts + 1 entries, first 0):
+ *   status[u]      KH_ALIGNC_DONE; KH_ALIGNC_NO_FINAL = no final state active on the last frame; KH_ALIGNC_NEEDS_ROOM =
+ *                  path_len[u] arcs do not fit the room: call again with that much (nothing is retried on the device);
+ *                  KH_ALIGNC_TOO_LARGE = the backpointers of this one utterance exceed the workspace limit; KH_ALIGNC_BOUND =
+ *                  a loop bound was hit: the eps closure still changed after states + 1 rounds (a negative eps cycle) or
+ *                  the backpointers did not lead to the start within (frames + 1) * states steps; KH_ALIGNC_BAD_INPUT = the
+ *                  graph was refused on the host (no start state, nextstate or ilabel out of range, a pdf outside the
+ *                  matrix's columns, a weight that is not finite): nothing of it is launched, kh_last_error() names the
+ *                  first such finding, the other utterances run.
+ *   total_cost[u]  the best token's cost_ plus its final weight, a double (DONE and NEEDS_ROOM; +inf otherwise)
+ *   best_state[u]  the state of that token, whose final weight GetBestPath puts on the path's end (:139-141); -1 otherwise
+ *   path_len[u], and at path_offsets[u] the path's arcs in path order: path_ilabel, path_olabel, path_graph = the arc's
+ *                  weight, path_acoustic = float(cost - prev cost) - graph, as GetBestPath forms them (:117-126).
+ * Offsets that do not describe a batch (decreasing, rows outside the matrix) refuse the call with KH_EINVAL, as do
+ * beam <= 0, min_active < 0 and beam_delta < 0.
+ * One workgroup per utterance; workspace per utterance in flight: (frames + 1) x states int32 backpointers, plus 2 x states
+ * doubles when the utterance has more states than the LDS admits (3584; kh_align_compiled_set_lds_states(n) lowers that for
+ * the calling thread, 0 = always the workspace - a test aid).  Utterances are taken largest first, as many per launch as half
+ * of the free device memory, or kh_align_compiled_set_workspace_limit(bytes) (calling thread; 0 = automatic), admits.
+ * kh_align_compiled_last_timings: milliseconds the last call of this thread spent in { host preparation, uploads, kernels,
+ * downloads (HIP events), the whole call by the host's clock }; counts3 (may be NULL) = { kernel launches, utterances whose
+ * costs lay in the workspace, utterances launched }. */
+#define KH_ALIGNC_DONE 0
+#define KH_ALIGNC_NO_FINAL 1
+#define KH_ALIGNC_NEEDS_ROOM 2
+#define KH_ALIGNC_TOO_LARGE 3
+#define KH_ALIGNC_BOUND 4
+#define KH_ALIGNC_BAD_INPUT 5
+int kh_align_compiled(int n_utts, const int32_t *state_offsets, const int64_t *arc_offsets, const int32_t *start,
+                      const int32_t *ilabel, const int32_t *olabel, const float *weight, const int32_t *nextstate,
+                      const float *final_w, int n_tid, const int32_t *tid2pdf, const float *loglikes, int ll_rows,
+                      int ll_cols, int ll_stride, const int32_t *utt_row_offsets, float beam, int min_active,
+                      float beam_delta, const int64_t *path_offsets, int32_t *status, double *total_cost,
+                      int32_t *best_state, int32_t *path_len, int32_t *path_ilabel, int32_t *path_olabel, float *path_graph,
+                      float *path_acoustic);
+int kh_align_compiled_set_workspace_limit(size_t bytes);
+int kh_align_compiled_set_lds_states(int max_states);
+int kh_align_compiled_last_timings(float *ms5, int32_t *counts3);
+
 /* LatticeForwardBackwardMpeVariants (lat/lattice-functions.cc:740-919): criterion
  * "smbr" (is_mpfe = 0) or "mpfe".  tid2phone / tid2pdf = TransitionIdToPhone /
  * TransitionIdToPdf as arrays of num_tids + 1 entries indexed by transition-id;

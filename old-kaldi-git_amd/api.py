@@ -2171,6 +2171,280 @@ def compact_lattice_align_words_last_timings():
                 launches=n[0], run_again=n[1], tuples=n[2])
 
 
+ALIGNC_DONE, ALIGNC_NO_FINAL, ALIGNC_NEEDS_ROOM, ALIGNC_TOO_LARGE, ALIGNC_BOUND, ALIGNC_BAD_INPUT = range(6)
+
+_libm = None
+
+
+def _libm_f(name):
+    """expf / logf of the C library: Exp and Log of base/kaldi-math.h for BaseFloat."""
+    global _libm
+    if _libm is None:
+        import ctypes.util
+        _libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    fn = getattr(_libm, name)
+    fn.restype, fn.argtypes = C.c_float, [C.c_float]
+    return lambda x: np.float32(fn(float(x)))
+
+
+def transition_id_to_state(tmodel):
+    """TransitionIdToTransitionState (hmm/transition-model.h:169): transition-states are the triples, numbered from 1, and
+    the transition-ids are numbered triple by triple (ComputeDerived :72-98).  Entry 0 unused (0)."""
+    out = [0]
+    for i, (phone, hmm_state, _) in enumerate(np.asarray(tmodel["triples"]).reshape(-1, 3)):
+        out += [i + 1] * len(tmodel["topo"]["entries"][tmodel["topo"]["phone2idx"][int(phone)]][int(hmm_state)][1])
+    return np.asarray(out, np.int32)
+
+
+def non_self_loop_log_probs(tmodel):
+    """ComputeDerivedOfProbs (hmm/transition-model.cc:255-272): per transition-state (entry 0 unused) Log(1 - Exp(log-prob of
+    the state's self-loop)) in float, 0 without a self-loop, Log(1e-10) where nothing is left."""
+    expf, logf = _libm_f("expf"), _libm_f("logf")
+    tstate, self_loop = transition_id_to_state(tmodel), np.asarray(tmodel["tid_is_self_loop"], bool)
+    log_probs = np.asarray(tmodel["log_probs"], np.float32)
+    out = np.zeros(int(tstate.max()) + 1 if len(tstate) > 1 else 1, np.float32)
+    for tid in range(1, len(tstate)):
+        if self_loop[tid]:
+            rest = np.float32(np.float32(1.0) - expf(log_probs[tid]))
+            if rest <= 0.0:
+                rest = np.float32(1.0e-10)
+            out[tstate[tid]] = logf(rest)
+    return out
+
+
+def add_transition_probs(graph, tmodel, transition_scale, self_loop_scale):
+    """AddTransitionProbs (hmm/hmm-utils.cc:776-830) with an empty list of disambiguation symbols, as gmm-align-compiled
+    and nnet-align-compiled call it: a copy of `graph` (the dict of kaldi_io.read_fst) whose arcs with a transition-id carry
+    weight - scaled log-prob; float arithmetic in the reference's order.  An ilabel outside 0..NumTransitionIds is an error
+    (:821-826)."""
+    log_probs = np.asarray(tmodel["log_probs"], np.float32)
+    num_tids = len(log_probs) - 1
+    ts, sl = np.float32(transition_scale), np.float32(self_loop_scale)
+    tstate, self_loop = transition_id_to_state(tmodel), np.asarray(tmodel["tid_is_self_loop"], bool)
+    il = np.asarray(graph["ilabel"], np.int32)
+    bad = il[(il < 0) | (il > num_tids)]
+    if len(bad):
+        raise KhError("AddTransitionProbs: invalid symbol %d on graph input side." % int(bad[0]))
+    scaled = np.zeros(num_tids + 1, np.float32)
+    if ts == sl:
+        scaled[1:] = log_probs[1:] * ts                                                     # :780-781
+    else:
+        nsl = non_self_loop_log_probs(tmodel)
+        for tid in range(1, num_tids + 1):
+            if self_loop[tid]:
+                scaled[tid] = sl * log_probs[tid]                                           # :783-784
+            else:
+                rest = nsl[tstate[tid]]
+                ignoring = np.float32(log_probs[tid] - rest)                                # transition-model.cc:333-337
+                scaled[tid] = np.float32(np.float32(sl * rest) + np.float32(ts * ignoring))   # :787-788
+    out = dict(graph)
+    w = np.asarray(graph["weight"], np.float32).copy()
+    emit = il != 0
+    w[emit] = w[emit] + (-scaled[il[emit]])                                                 # Times :820
+    out["weight"] = w
+    return out
+
+
+def modify_graph_for_careful_alignment(graph):
+    """ModifyGraphForCarefulAlignment (decoder/decoder-wrappers.cc:393-420) on the dict of kaldi_io.read_fst.  The
+    reference concatenates the graph with a copy of itself that has no final weights and a new start state, final with
+    weight One, in front (an eps arc of weight One to the copy's old start).  fst::Concat gives every final state of the
+    left side an eps arc with its final weight to the right side's start and takes its final weight away.  Here: states
+    0..S-1 the graph, S..2S-1 the copy, 2S the new state - the only final one.  (The numbering is the library's own; only
+    labels leave the alignment.)"""
+    S = int(graph["num_states"])
+    if S == 0:
+        return dict(graph)
+    off = np.asarray(graph["arc_offsets"], np.int64)
+    il, ol = np.asarray(graph["ilabel"], np.int32), np.asarray(graph["olabel"], np.int32)
+    w, ns = np.asarray(graph["weight"], np.float32), np.asarray(graph["nextstate"], np.int32)
+    fin = np.asarray(graph["final"], np.float32)
+    is_final = fin != np.float32(np.inf)
+    pre = 2 * S
+    n_il, n_ol, n_w, n_ns, n_off = [], [], [], [], [0]
+    for s in range(S):                                   # the graph: its arcs, then the arc that Concat adds
+        a0, a1 = int(off[s]), int(off[s + 1])
+        n_il.append(il[a0:a1]); n_ol.append(ol[a0:a1]); n_w.append(w[a0:a1]); n_ns.append(ns[a0:a1])
+        if is_final[s]:
+            n_il.append(np.zeros(1, np.int32)); n_ol.append(np.zeros(1, np.int32)); n_w.append(fin[s:s + 1]); n_ns.append(np.asarray([pre], np.int32))
+        n_off.append(n_off[-1] + (a1 - a0) + int(is_final[s]))
+    for s in range(S):                                   # the copy
+        a0, a1 = int(off[s]), int(off[s + 1])
+        n_il.append(il[a0:a1]); n_ol.append(ol[a0:a1]); n_w.append(w[a0:a1]); n_ns.append(ns[a0:a1] + S)
+        n_off.append(n_off[-1] + (a1 - a0))
+    n_il.append(np.zeros(1, np.int32)); n_ol.append(np.zeros(1, np.int32)); n_w.append(np.zeros(1, np.float32))
+    n_ns.append(np.asarray([S + int(graph["start"])], np.int32))
+    n_off.append(n_off[-1] + 1)
+    final = np.full(2 * S + 1, np.inf, np.float32)
+    final[pre] = 0.0
+    cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs).astype(dt))
+    out = dict(graph)
+    out.update(num_states=2 * S + 1, start=int(graph["start"]), arc_offsets=np.asarray(n_off, np.int64), ilabel=cat(n_il, np.int32),
+               olabel=cat(n_ol, np.int32), weight=cat(n_w, np.float32), nextstate=cat(n_ns, np.int32), final=final)
+    return out
+
+
+def align_compiled_pack(graphs):
+    """The graph arguments of kh_align_compiled: the CSR dicts of kaldi_io.read_fst concatenated."""
+    n = len(graphs)
+    soff = np.zeros(n + 1, np.int32)
+    soff[1:] = np.cumsum([int(g["num_states"]) for g in graphs])
+    aoff, base = [np.zeros(1, np.int64)], 0
+    for g in graphs:
+        o = np.asarray(g["arc_offsets"], np.int64).reshape(-1)
+        if len(o) != int(g["num_states"]) + 1:
+            raise KhError("align_compiled: a graph's arc_offsets do not have num_states + 1 entries")
+        aoff.append(o[1:] + base)
+        base += int(o[-1]) if len(o) else 0
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(g[k], dt).reshape(-1) for g in graphs] + [np.zeros(0, dt)]))
+    A = dict(state_offsets=soff, arc_offsets=np.ascontiguousarray(np.concatenate(aoff)),
+             start=np.ascontiguousarray(np.asarray([int(g["start"]) for g in graphs], np.int32)), ilabel=cat("ilabel", np.int32),
+             olabel=cat("olabel", np.int32), weight=cat("weight", np.float32), nextstate=cat("nextstate", np.int32),
+             final=cat("final", np.float32))
+    for k in ("ilabel", "olabel", "weight", "nextstate"):
+        if len(A[k]) != base:
+            raise KhError("align_compiled: %d entries of %s for %d arcs" % (len(A[k]), k, base))
+    if len(A["final"]) != int(soff[-1]):
+        raise KhError("align_compiled: %d final weights for %d states" % (len(A["final"]), int(soff[-1])))
+    return A
+
+
+def align_compiled_call(A, loglikes, row_offsets, tid2pdf, beam, min_active, beam_delta, room):
+    """One kh_align_compiled call on align_compiled_pack's arrays; loglikes a 2-D float32 device tensor, room = path room
+    per utterance.  Returns dict(status, cost, path_len, path_offsets, ilabel, olabel, graph, acoustic)."""
+    n = len(A["start"])
+    _dim(loglikes)
+    ro = np.ascontiguousarray(np.asarray(row_offsets, np.int32).reshape(-1))
+    if len(ro) != n + 1:
+        raise KhError("align_compiled: %d row offsets for %d utterances" % (len(ro), n))
+    t2p = None if tid2pdf is None else np.ascontiguousarray(np.asarray(tid2pdf, np.int32).reshape(-1))
+    n_tid = len(t2p) if t2p is not None else int(loglikes.shape[1]) + 1
+    po = np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.asarray(room, np.int64).reshape(n))]).astype(np.int64))
+    status, plen, best, cost = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+    m = max(int(po[-1]), 1)
+    p_il, p_ol, p_g, p_a = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+    ip, fp, lp = capi.c_int32_p, capi.c_float_p, capi.c_int64_p
+    ptr = lambda x, t: x.ctypes.data_as(t)
+    check(lib().kh_align_compiled(
+        n, ptr(A["state_offsets"], ip), ptr(A["arc_offsets"], lp), ptr(A["start"], ip), ptr(A["ilabel"], ip), ptr(A["olabel"], ip),
+        ptr(A["weight"], fp), ptr(A["nextstate"], ip), ptr(A["final"], fp), n_tid, None if t2p is None else ptr(t2p, ip),
+        _p(loglikes), int(loglikes.shape[0]), int(loglikes.shape[1]), int(loglikes.stride(0)) if loglikes.shape[0] > 1 else int(loglikes.shape[1]),
+        ptr(ro, ip), float(beam), int(min_active), float(beam_delta), ptr(po, lp), ptr(status, ip), ptr(cost, capi.c_double_p),
+        ptr(best, ip), ptr(plen, ip), ptr(p_il, ip), ptr(p_ol, ip), ptr(p_g, fp), ptr(p_a, fp)))
+    return dict(status=status, cost=cost, best_state=best, path_len=plen, path_offsets=po, ilabel=p_il, olabel=p_ol, graph=p_g, acoustic=p_a)
+
+
+def align_compiled_raw(graphs, loglikes, row_offsets, tid2pdf, beam, min_active=20, beam_delta=0.5, workspace_limit=None,
+                       path_room=None):
+    """One Decode() per utterance (kh_align_compiled) and, for the utterances whose path did not fit the room, one more call
+    with the room they named.  path_room: None = 2 x frames + 16 arcs per utterance (a training graph has two or three eps arcs per word), or a
+    number per utterance.  Returns per
+    utterance dict(status, cost, best_state, path [(ilabel, olabel, graph_cost, ac_cost)], path_len)."""
+    n = len(graphs)
+    if n == 0:
+        raise KhError("align_compiled: no utterances")
+    ro = np.asarray(row_offsets, np.int64).reshape(-1)
+    frames = np.diff(ro)
+    room = 2 * frames + 16 if path_room is None else np.broadcast_to(np.asarray(path_room, np.int64), (n,))
+    if workspace_limit is not None:
+        check(lib().kh_align_compiled_set_workspace_limit(int(workspace_limit)))
+    try:
+        out = [None] * n
+        todo = list(range(n))
+        for attempt in range(2):
+            A = align_compiled_pack([graphs[u] for u in todo])
+            sub_ro = np.concatenate([[0], np.cumsum(frames[todo])])
+            if len(todo) == n:
+                ll, sub_ro = loglikes, ro
+            else:   # the rows of the utterances that go again, gathered (torch owns the memory; nothing is computed)
+                ll = torch.cat([loglikes[int(ro[u]):int(ro[u + 1])] for u in todo]) if int(sub_ro[-1]) > 0 else loglikes[:0]
+                ll = ll.contiguous()
+            R = align_compiled_call(A, ll, sub_ro, tid2pdf, beam, min_active, beam_delta, np.asarray(room)[todo])
+            again = []
+            for k, u in enumerate(todo):
+                st, p0, ln = int(R["status"][k]), int(R["path_offsets"][k]), int(R["path_len"][k])
+                if st == ALIGNC_NEEDS_ROOM and attempt == 0:
+                    room = np.array(room, np.int64)
+                    room[u] = ln
+                    again.append(u)
+                    continue
+                path = []
+                if st == ALIGNC_DONE:
+                    path = [(int(R["ilabel"][p0 + i]), int(R["olabel"][p0 + i]), R["graph"][p0 + i], R["acoustic"][p0 + i]) for i in range(ln)]
+                out[u] = dict(status=st, cost=float(R["cost"][k]), best_state=int(R["best_state"][k]), path=path, path_len=ln)
+            todo = again
+            if not todo:
+                break
+    finally:
+        if workspace_limit is not None:
+            check(lib().kh_align_compiled_set_workspace_limit(0))
+    return out
+
+
+def linear_symbol_sequence(path, final_weight):
+    """GetLinearSymbolSequence (fstext/fstext-utils-inl.h) on the linear best path: the nonzero ilabels, the nonzero olabels
+    and the Times of the arcs' LatticeWeights in path order with the final weight last, float sums."""
+    g = a = np.float32(0.0)
+    for (_, _, pg, pa) in path:
+        g, a = np.float32(g + np.float32(pg)), np.float32(a + np.float32(pa))
+    g = np.float32(g + np.float32(final_weight))
+    return [x[0] for x in path if x[0] != 0], [x[1] for x in path if x[1] != 0], (g, a)
+
+
+def align_compiled(graphs, loglikes, row_offsets, tid2pdf, beam, retry_beam=0.0, careful=False, min_active=20, beam_delta=0.5,
+                   workspace_limit=None, path_room=None):
+    """AlignUtteranceWrapper (decoder/decoder-wrappers.cc:423-505) for a batch: graphs = the utterances' decoding graphs
+    (dicts of kaldi_io.read_fst, transition probabilities already added), loglikes = the scaled log-likelihoods of all
+    utterances as one 2-D float32 device tensor, utterance u at rows row_offsets[u]..row_offsets[u+1], tid2pdf indexed by
+    transition-id (None = ilabel - 1).  The search is FasterDecoder by the rule of include/kaldi_hip.h at kh_align_compiled.
+    The utterances that reach no final state with `beam` are searched once more with `retry_beam` (0 = not), in a second
+    call over them alone.  Returns per utterance dict(status [ALIGNC_*], retried, alignment, words, cost [the double total],
+    weight [(graph, acoustic) floats, the final weight in graph], like [float -(graph + acoustic), the value of the scores
+    table], path)."""
+    beam, retry_beam = float(beam), float(retry_beam)
+    if (retry_beam != 0 and retry_beam <= beam) or beam <= 0.0:                           # :439-443
+        raise KhError("Beams do not make sense: beam %g, retry-beam %g" % (beam, retry_beam))
+    if careful:
+        graphs = [modify_graph_for_careful_alignment(g) for g in graphs]
+    res = align_compiled_raw(graphs, loglikes, row_offsets, tid2pdf, beam, min_active, beam_delta, workspace_limit, path_room)
+    for r in res:
+        r["retried"] = False
+    again = [u for u, r in enumerate(res) if r["status"] == ALIGNC_NO_FINAL]
+    if again and retry_beam != 0:                                                          # :464-472
+        ro = np.asarray(row_offsets, np.int64).reshape(-1)
+        frames = np.diff(ro)[again]
+        sub_ro = np.concatenate([[0], np.cumsum(frames)])
+        ll = torch.cat([loglikes[int(ro[u]):int(ro[u + 1])] for u in again]).contiguous() if int(sub_ro[-1]) > 0 else loglikes[:0]
+        room = None if path_room is None else np.broadcast_to(np.asarray(path_room, np.int64), (len(graphs),))[again]
+        sub = align_compiled_raw([graphs[u] for u in again], ll, sub_ro, tid2pdf, retry_beam, min_active, beam_delta, workspace_limit, room)
+        for u, r in zip(again, sub):
+            r["retried"] = True
+            res[u] = r
+    for u, r in enumerate(res):
+        r["alignment"], r["words"], r["weight"], r["like"] = [], [], None, None
+        if r["status"] == ALIGNC_DONE:
+            r["alignment"], r["words"], r["weight"] = linear_symbol_sequence(r["path"], graphs[u]["final"][r["best_state"]])
+            r["like"] = np.float32(-np.float32(r["weight"][0] + r["weight"][1]))
+    return res
+
+
+def align_compiled_set_lds_states(max_states):
+    """Utterances with more states than this keep their token costs in the call's workspace instead of LDS (calling
+    thread; at most 3584, the default; 0 = always the workspace).  A test and measurement aid."""
+    check(lib().kh_align_compiled_set_lds_states(int(max_states)))
+
+
+def align_compiled_last_timings():
+    """Milliseconds the last kh_align_compiled call of this thread spent in host preparation / uploads / kernels / downloads
+    and in the whole call, and the number of kernel launches, of utterances whose costs lay in the workspace and of
+    utterances launched."""
+    ms = (C.c_float * 5)()
+    n = (C.c_int32 * 3)()
+    check(lib().kh_align_compiled_last_timings(ms, n))
+    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n[0],
+                workspace_cost_utts=n[1], utts_launched=n[2])
+
+
 def rescore_lattice(lats, loglikes, utt_row_offsets, tid2pdf=None):
     """RescoreLattice (lat/lattice-functions.cc:1307-1358) for a batch: loglikes = device
     matrix (rows of lattice i at utt_row_offsets[i]...).  Returns the new arc_acoustic arrays."""

@@ -1215,6 +1215,62 @@ int kh_ivector_streams_update_frame_weights(KhIvectorStreams *s, int stream, int
 int kh_ivector_streams_get_frames(KhIvectorStreams *s, int n, const int32_t *streams, const int32_t *until_frame);
 int kh_ivector_streams_get_stats(const KhIvectorStreams *s, double *states_out);
 
+/* ------------------------------------------------------------------ fMLLR estimation (csrc/kh_fmllr.hip)
+ * gmm-est-fmllr / gmm-est-fmllr-gpost / gmm-post-to-gpost for a batch of speakers, in four stages with explicit inputs and
+ * outputs.  A per-utterance run is one speaker per utterance.  Common layout: the frames of all utterances stacked by rows
+ * (feats: DEVICE, T x D, row pitch feat_stride); utt_row_offsets[n_utts + 1] and spk_utt_offsets[n_spk + 1] HOST, a
+ * speaker's utterances contiguous in spk2utt order; the (frame, pdf) entries in CSR form over frames, HOST:
+ * frame_entry_offsets[T + 1], entry_pdf[], entry_weight[]; within a frame in ascending pdf order by convention (the
+ * reference's order is an unordered_map's; the library takes the order given).  entry_gauss_offsets[E + 1] HOST: the running
+ * sum of the entries' pdf sizes, built by the caller and checked here.  Model arrays (gconsts, means_invvars, inv_vars) DEVICE
+ * as kh_diag_gmm_loglikes takes them, pdf_offsets[num_pdfs + 1] HOST.  Every index is checked on the host before a launch.
+ *
+ * A1  DiagGmm::ComponentPosteriors (gmm/diag-gmm.cc:601-615) with VectorBase::ApplySoftMax (matrix/kaldi-vector.cc:840-847)
+ *     and the Scale(weight) of FmllrDiagGmmAccs::AccumulateForGmm (transform/fmllr-diag-gmm.cc:108-109), per entry:
+ *     gauss_post (DEVICE, entry_gauss_offsets[E] floats) = softmax of the entry's per-Gaussian scores times its weight,
+ *     entry_like (DEVICE, E floats) = max + log(sum), the value gmm-post-to-gpost sums (gmm-post-to-gpost.cc:118-121).
+ *     Scores: kh_diag_gmm_loglikes's fmaf chains, bit for bit; then float max, fl32(f - max), expf, float sum in Gaussian
+ *     order, times fl32(1.0 / sum), times the weight; expf and logf are the device math library's. */
+int kh_gmm_component_posteriors(const float *feats, int T, int D, int feat_stride, const float *gconsts,
+                                const float *means_invvars, const float *inv_vars, const int32_t *pdf_offsets, int num_pdfs,
+                                const int64_t *frame_entry_offsets, const int32_t *entry_pdf, const float *entry_weight,
+                                const int64_t *entry_gauss_offsets, float *gauss_post, float *entry_like);
+/* A2  FmllrDiagGmmAccs::AccumulateFromPosteriors (fmllr-diag-gmm.cc:30-43) for given Gaussian posteriors (DEVICE) and a
+ *     model's means_invvars / inv_vars - the model of A1, or another one with the same Gaussian counts (the two-model case of
+ *     gmm-est-fmllr-gpost.cc:36-52); KH_EINVAL naming the pdf where a count differs.  Output per MERGED FRAME, restating
+ *     DataHasChanged / InitSingleFrameStats / CommitSingleFrameStats (:542-596): within a speaker, over the frames that have
+ *     entries and across its utterance boundaries, a frame whose row equals (float ==, every element) the previous such frame's
+ *     row joins it; the entries are concatenated.  HOST outputs: run_row[] (the first row of each merged frame; room for T),
+ *     spk_run_offsets[n_spk + 1].  DEVICE outputs, room for T merged frames: a, b [. x D] float (fmaf chains over the merged
+ *     frame's entries in order, each entry's Gaussians in order), count [.] double (adds each entry's float posterior sum). */
+int kh_fmllr_frame_stats(const float *feats, int T, int D, int feat_stride, const float *means_invvars, const float *inv_vars,
+                         const int32_t *pdf_offsets, int num_pdfs, const int32_t *utt_row_offsets, int n_utts,
+                         const int32_t *spk_utt_offsets, int n_spk, const int64_t *frame_entry_offsets, const int32_t *entry_pdf,
+                         const int64_t *entry_gauss_offsets, const float *gauss_post, int32_t *run_row, int32_t *spk_run_offsets,
+                         float *a, float *b, double *count);
+/* B   FmllrDiagGmmAccs::CommitSingleFrameStats (fmllr-diag-gmm.cc:562-596, update type "full") over every speaker's merged
+ *     frames, in double: beta[n_spk], K[n_spk][D][D + 1], G[n_spk][D][(D + 1)(D + 2) / 2] (SpMatrix packing: (r, c), r >= c, at
+ *     r (r + 1) / 2 + c), HOST outputs.  A merged frame whose count is 0 adds nothing (:566).  fp64 matrix-core GEMM with the
+ *     scatter operand made on the fly; partial sums per chunk of kh_fmllr_frame_chunk merged frames, added in chunk order: the
+ *     same input gives the same bits.  D = 1 ... kh_fmllr_max_dim (63); above: KH_EINVAL before any launch. */
+int kh_fmllr_accumulate(const float *feats, int T, int D, int feat_stride, const int32_t *run_row, const int32_t *spk_run_offsets,
+                        int n_spk, const float *a, const float *b, const double *count, double *beta, double *K, double *G);
+/* C   FmllrDiagGmmAccs::Update (fmllr-diag-gmm.cc:131-166) from a unit transform, per speaker: ComputeFmllrMatrixDiagGmmFull
+ *     with FmllrInnerUpdate (:193-273), ...Diagonal (:275-348), ...Offset (:350-378), "none", FmllrAuxFuncDiagGmm (:481-508);
+ *     min_count and "objective function did not increase -> keep" included.  HOST code in double, needs no device;
+ *     num_threads <= 16 threads over speakers (0 = 16).  transforms [n_spk][D][D + 1] float, objf_impr, count [n_spk] float.
+ *     "diag" and "offset" read only the three elements per G_i that the reference would have accumulated for them. */
+int kh_fmllr_update(int n_spk, int D, const double *beta, const double *K, const double *G, const char *update_type, float min_count,
+                    int num_iters, int num_threads, float *transforms, float *objf_impr, float *count);
+int kh_fmllr_max_dim(void);
+int kh_fmllr_frame_chunk(void);
+/* B takes the speakers in groups whose workspace (one partial sum per chunk and one sum per speaker, D P + D (D + 1) doubles
+ * each) stays within this many bytes (calling thread; 0 = the default, 1 GiB); a speaker is never split.  No sum depends on it. */
+int kh_fmllr_set_workspace_limit(size_t bytes);
+/* ms[6]: milliseconds of the calling thread's last A1, A2, B and C calls (whole call, transfers and waits included), of B's
+ * kernels alone (device events), and the number of speaker groups B took. */
+int kh_fmllr_last_timings(float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3057,3 +3057,283 @@ class OnlineNnet2FeaturePipeline:
                 out[off[u]:off[u + 1], d0:] = iv[boff[j]:boff[j + 1]]
             r += 1
         return out, off
+
+
+# ---------------------------------------------------------------- fMLLR estimation (csrc/kh_fmllr.hip)
+# gmm-est-fmllr, gmm-est-fmllr-gpost and gmm-post-to-gpost for a batch of speakers, in the library's four stages.  The frames
+# of all utterances are stacked by rows; an entry list is CSR over those frames: dict(feo [T + 1] int64, pdf [E] int32,
+# weight [E] float32, goff [E + 1] int64 = the running sum of the entries' pdf sizes).
+def _host_pdf_offsets(am):
+    return np.ascontiguousarray(am.pdf_offsets.cpu().numpy(), np.int32)
+
+
+def _feat_args(feats):
+    _dim(feats)
+    T, D = int(feats.shape[0]), int(feats.shape[1])
+    return T, D, int(feats.stride(0)) if T > 1 else max(int(feats.stride(0)), D)
+
+
+def fmllr_entries(pdf_posts, pdf_offsets):
+    """The entry list of a Posterior over pdfs: a list over the stacked frames of [(pdf, weight), ...], each frame in the
+    order given (convert_posterior_to_pdfs gives ascending pdfs)."""
+    off = np.asarray(pdf_offsets, np.int64)
+    feo = np.zeros(len(pdf_posts) + 1, np.int64)
+    pdf, w = [], []
+    for t, fr in enumerate(pdf_posts):
+        for p, x in fr:
+            pdf.append(int(p))
+            w.append(x)
+        feo[t + 1] = len(pdf)
+    pdf = np.ascontiguousarray(pdf, np.int32)
+    if len(pdf) and (pdf.min() < 0 or pdf.max() >= len(off) - 1):
+        raise KhError("fmllr_entries: pdf %d, the model has %d" % (int(pdf.max() if pdf.min() >= 0 else pdf.min()), len(off) - 1))
+    goff = np.zeros(len(pdf) + 1, np.int64)
+    if len(pdf):
+        goff[1:] = np.cumsum(off[pdf + 1] - off[pdf])
+    return dict(feo=feo, pdf=pdf, weight=np.ascontiguousarray(w, np.float32), goff=goff)
+
+
+def _entry_ptrs(ent, T):
+    feo = np.ascontiguousarray(ent["feo"], np.int64)
+    pdf = np.ascontiguousarray(ent["pdf"], np.int32)
+    goff = np.ascontiguousarray(ent["goff"], np.int64)
+    if len(feo) != T + 1 or len(goff) != len(pdf) + 1 or int(feo[-1]) != len(pdf):
+        raise KhError("fmllr: entry list of %d frames / %d entries against %d frames" % (len(feo) - 1, len(pdf), T))
+    return feo, pdf, goff
+
+
+def gmm_component_posteriors(am, feats, ent):
+    """DiagGmm::ComponentPosteriors (gmm/diag-gmm.cc:601-615) times the entry's weight, per entry (kh_gmm_component_posteriors).
+    am: AmDiagGmm; feats: 2-D float32 device tensor.  Returns (gauss_post, like): device tensors of goff[E] and E floats."""
+    T, D, stride = _feat_args(feats)
+    if D != am.dim:
+        raise KhError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (D, am.dim))
+    feo, pdf, goff = _entry_ptrs(ent, T)
+    w = np.ascontiguousarray(ent["weight"], np.float32)
+    if len(w) != len(pdf):
+        raise KhError("fmllr: %d weights for %d entries" % (len(w), len(pdf)))
+    off = _host_pdf_offsets(am)
+    post = torch.zeros(max(int(goff[-1]), 1), dtype=torch.float32, device=feats.device)
+    like = torch.zeros(max(len(pdf), 1), dtype=torch.float32, device=feats.device)
+    ip, lp = capi.c_int32_p, capi.c_int64_p
+    check(lib().kh_gmm_component_posteriors(_p(feats), T, D, stride, _p(am.gconsts), _p(am.means_invvars), _p(am.inv_vars),
+                                            off.ctypes.data_as(ip), am.num_pdfs, feo.ctypes.data_as(lp), pdf.ctypes.data_as(ip),
+                                            w.ctypes.data_as(capi.c_float_p), goff.ctypes.data_as(lp), _p(post), _p(like)))
+    return post[:int(goff[-1])], like[:len(pdf)]
+
+
+def fmllr_frame_stats(am, feats, utt_row_offsets, spk_utt_offsets, ent, gauss_post):
+    """FmllrDiagGmmAccs::AccumulateFromPosteriors per merged frame (kh_fmllr_frame_stats; the merging rule is stated in
+    include/kaldi_hip.h).  am: the model whose means_invvars / inv_vars are accumulated.  Returns dict(run_row,
+    spk_run_offsets [host], a, b [R x D float32 device], count [R float64 device])."""
+    T, D, stride = _feat_args(feats)
+    if D != am.dim:
+        raise KhError("fmllr_frame_stats: feature dimension %d, model dimension %d" % (D, am.dim))
+    feo, pdf, goff = _entry_ptrs(ent, T)
+    uro = np.ascontiguousarray(np.asarray(utt_row_offsets, np.int32).reshape(-1))
+    suo = np.ascontiguousarray(np.asarray(spk_utt_offsets, np.int32).reshape(-1))
+    if gauss_post.numel() != int(goff[-1]) or gauss_post.dtype != torch.float32 or not gauss_post.is_cuda:
+        raise KhError("fmllr_frame_stats: %d Gaussian posteriors for entries that hold %d" % (gauss_post.numel(), int(goff[-1])))
+    gauss_post = gauss_post.contiguous()
+    off = _host_pdf_offsets(am)
+    n_spk = len(suo) - 1
+    run_row, spk_run = np.zeros(T, np.int32), np.zeros(n_spk + 1, np.int32)
+    a = torch.zeros((T, D), dtype=torch.float32, device=feats.device)
+    b = torch.zeros((T, D), dtype=torch.float32, device=feats.device)
+    count = torch.zeros(T, dtype=torch.float64, device=feats.device)
+    ip, lp = capi.c_int32_p, capi.c_int64_p
+    check(lib().kh_fmllr_frame_stats(_p(feats), T, D, stride, _p(am.means_invvars), _p(am.inv_vars), off.ctypes.data_as(ip),
+                                     am.num_pdfs, uro.ctypes.data_as(ip), len(uro) - 1, suo.ctypes.data_as(ip), n_spk,
+                                     feo.ctypes.data_as(lp), pdf.ctypes.data_as(ip), goff.ctypes.data_as(lp), _p(gauss_post),
+                                     run_row.ctypes.data_as(ip), spk_run.ctypes.data_as(ip), _p(a), _p(b), _p(count)))
+    R = int(spk_run[-1])
+    return dict(run_row=run_row[:R].copy(), spk_run_offsets=spk_run, a=a[:R], b=b[:R], count=count[:R])
+
+
+def fmllr_accumulate(feats, fs):
+    """CommitSingleFrameStats over every speaker's merged frames (kh_fmllr_accumulate): dict(beta [S], K [S, D, D + 1],
+    G [S, D, (D + 1)(D + 2) / 2]) float64 host arrays, G in SpMatrix packing."""
+    T, D, stride = _feat_args(feats)
+    run_row = np.ascontiguousarray(fs["run_row"], np.int32)
+    spk_run = np.ascontiguousarray(fs["spk_run_offsets"], np.int32)
+    S, R, P = len(spk_run) - 1, len(run_row), (D + 1) * (D + 2) // 2
+    a, b, count = fs["a"].contiguous(), fs["b"].contiguous(), fs["count"].contiguous()
+    if int(spk_run[-1]) != R or (R and (tuple(a.shape) != (R, D) or tuple(b.shape) != (R, D) or count.numel() != R)):
+        raise KhError("fmllr_accumulate: %d merged frames, a %s, b %s, count %d" % (R, tuple(a.shape), tuple(b.shape), count.numel()))
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and count.dtype == torch.float64
+    beta, K, G = np.zeros(S, np.float64), np.zeros((S, D, D + 1), np.float64), np.zeros((S, D, P), np.float64)
+    ip, dp = capi.c_int32_p, capi.c_double_p
+    check(lib().kh_fmllr_accumulate(_p(feats), T, D, stride, run_row.ctypes.data_as(ip), spk_run.ctypes.data_as(ip), S,
+                                    _p(a) if R else None, _p(b) if R else None, _p(count) if R else None,
+                                    beta.ctypes.data_as(dp), K.ctypes.data_as(dp), G.ctypes.data_as(dp)))
+    return dict(beta=beta, K=K, G=G)
+
+
+def fmllr_options(update_type="full", min_count=500.0, num_iters=40):
+    """FmllrOptions (transform/fmllr-diag-gmm.h:43-56) with the reference's defaults."""
+    return dict(update_type=update_type, min_count=float(min_count), num_iters=int(num_iters))
+
+
+def fmllr_update(stats, update_type="full", min_count=500.0, num_iters=40, num_threads=0):
+    """FmllrDiagGmmAccs::Update from a unit transform per speaker (kh_fmllr_update, host code).  Returns (transforms
+    [S, D, D + 1] float32, objf_impr [S] float32, count [S] float32)."""
+    beta = np.ascontiguousarray(stats["beta"], np.float64)
+    K = np.ascontiguousarray(stats["K"], np.float64)
+    G = np.ascontiguousarray(stats["G"], np.float64)
+    S, D = K.shape[0], K.shape[1]
+    if K.shape != (S, D, D + 1) or G.shape != (S, D, (D + 1) * (D + 2) // 2) or beta.shape != (S,):
+        raise KhError("fmllr_update: stats of shapes %s %s %s" % (beta.shape, K.shape, G.shape))
+    W, impr, count = np.zeros((S, D, D + 1), np.float32), np.zeros(S, np.float32), np.zeros(S, np.float32)
+    dp, fp = capi.c_double_p, capi.c_float_p
+    check(lib().kh_fmllr_update(S, D, beta.ctypes.data_as(dp), K.ctypes.data_as(dp), G.ctypes.data_as(dp), update_type.encode(),
+                                float(min_count), int(num_iters), int(num_threads), W.ctypes.data_as(fp), impr.ctypes.data_as(fp),
+                                count.ctypes.data_as(fp)))
+    return W, impr, count
+
+
+def fmllr_max_dim():
+    return int(lib().kh_fmllr_max_dim())
+
+
+def fmllr_frame_chunk():
+    """Merged frames per workgroup of the accumulation kernel (kFrameChunk of csrc/kh_fmllr.hip)."""
+    return int(lib().kh_fmllr_frame_chunk())
+
+
+def fmllr_set_workspace_limit(nbytes):
+    """fmllr_accumulate takes the speakers in groups whose workspace stays within nbytes (calling thread; 0 = 1 GiB)."""
+    check(lib().kh_fmllr_set_workspace_limit(int(nbytes)))
+
+
+def fmllr_last_timings():
+    """Milliseconds of this thread's last calls of the four stages (whole calls, transfers and waits included)."""
+    ms = (C.c_float * 6)()
+    check(lib().kh_fmllr_last_timings(ms))
+    return dict(component_posteriors_ms=ms[0], frame_stats_ms=ms[1], accumulate_ms=ms[2], update_ms=ms[3],
+                accumulate_kernels_ms=ms[4], accumulate_groups=int(ms[5]))
+
+
+def estimate_fmllr(am, feats, utt_row_offsets, spk_utt_offsets, posts=None, gposts=None, tid2pdf=None, opts=None, gpost_am=None,
+                   return_stats=False):
+    """gmm-est-fmllr (posts) or gmm-est-fmllr-gpost (gposts) for all speakers in one pass.  feats: the utterances' frames
+    stacked, 2-D float32 device tensor; a speaker's utterances contiguous (spk_utt_offsets over utt_row_offsets).
+    posts: a Posterior over the stacked frames, [(id, weight), ...] per frame, ids = transition-ids mapped through tid2pdf
+    (None: they are pdf-ids already).  gposts: per frame [(pdf, posteriors array), ...] as gmm-post-to-gpost writes them; the
+    statistics are then taken with gpost_am's means / variances when given (the two-model case), else am's.
+    opts: fmllr_options().  Returns (transforms [S, D, D + 1], objf_impr [S], count [S]) (+ the statistics)."""
+    if (posts is None) == (gposts is None):
+        raise KhError("estimate_fmllr: give posts or gposts")
+    opts = opts or fmllr_options()
+    off = _host_pdf_offsets(am)
+    if posts is not None:
+        pdf_posts = convert_posterior_to_pdfs(tid2pdf, posts) if tid2pdf is not None else posts
+        ent = fmllr_entries(pdf_posts, off)
+        gauss_post, _ = gmm_component_posteriors(am, feats, ent)
+        acc_am = am
+    else:
+        acc_am = gpost_am if gpost_am is not None else am
+        sizes = np.diff(off.astype(np.int64))
+        feo = np.zeros(len(gposts) + 1, np.int64)
+        pdf, vecs = [], []
+        for t, fr in enumerate(gposts):
+            for p, v in fr:
+                v = np.asarray(v, np.float32).reshape(-1)
+                if not 0 <= int(p) < len(sizes) or len(v) != sizes[int(p)]:
+                    raise KhError("estimate_fmllr: pdf %d has %s Gaussians, the gpost carries %d" %
+                                  (int(p), sizes[int(p)] if 0 <= int(p) < len(sizes) else "no", len(v)))
+                pdf.append(int(p))
+                vecs.append(v)
+            feo[t + 1] = len(pdf)
+        goff = np.zeros(len(pdf) + 1, np.int64)
+        if pdf:
+            goff[1:] = np.cumsum([len(v) for v in vecs])
+        ent = dict(feo=feo, pdf=np.ascontiguousarray(pdf, np.int32), weight=np.ones(len(pdf), np.float32), goff=goff)
+        flat = np.concatenate(vecs) if vecs else np.zeros(0, np.float32)
+        gauss_post = torch.as_tensor(flat, device=feats.device)
+    fs = fmllr_frame_stats(acc_am, feats, utt_row_offsets, spk_utt_offsets, ent, gauss_post)
+    stats = fmllr_accumulate(feats, fs)
+    W, impr, count = fmllr_update(stats, opts["update_type"], opts["min_count"], opts["num_iters"])
+    return (W, impr, count, stats) if return_stats else (W, impr, count)
+
+
+def gmm_post_to_gpost(am, feats, pdf_posts):
+    """gmm-post-to-gpost.cc:94-115 for the stacked frames: per frame [(pdf, posteriors), ...] without the vectors that are
+    zero (IsZero's 1e-6 cutoff), and per entry (like, weight) for the tool's averages."""
+    ent = fmllr_entries(pdf_posts, _host_pdf_offsets(am))
+    post, like = gmm_component_posteriors(am, feats, ent)
+    post, like = post.cpu().numpy(), like.cpu().numpy()
+    out = []
+    for t in range(len(pdf_posts)):
+        fr = []
+        for e in range(int(ent["feo"][t]), int(ent["feo"][t + 1])):
+            v = post[int(ent["goff"][e]):int(ent["goff"][e + 1])]
+            if np.abs(v).max() > 1.0e-06:                                                  # !this_post_vec.IsZero()
+                fr.append((int(ent["pdf"][e]), v.copy()))
+        out.append(fr)
+    return out, like, ent["weight"]
+
+
+# ---- host posterior / transform algebra of the fMLLR recipes
+def weight_silence_post(tid2phone, silence_phones, silence_scale, post, distribute=False):
+    """WeightSilencePost / WeightSilencePostDistributed (hmm/posterior.cc:361-413): tid2phone indexed by transition-id."""
+    sil = set(int(p) for p in silence_phones)
+    f32 = np.float32
+    scale = f32(silence_scale)
+    out = []
+    for fr in post:
+        if not distribute:
+            this = []
+            for tid, w in fr:
+                if int(tid2phone[tid]) in sil:
+                    if scale != 0.0:
+                        this.append((tid, float(f32(f32(w) * scale))))
+                else:
+                    this.append((tid, float(f32(w))))
+            out.append(this)
+            continue
+        sw, nw = f32(0.0), f32(0.0)
+        for tid, w in fr:
+            if int(tid2phone[tid]) in sil:
+                sw = f32(sw + f32(w))
+            else:
+                nw = f32(nw + f32(w))
+        if sw < 0.0 or nw < 0.0:
+            raise KhError("KALDI_ASSERT: sil_weight >= 0.0 && nonsil_weight >= 0.0")
+        if f32(sw + nw) == 0.0:
+            out.append(list(fr))
+            continue
+        fscale = f32(f32(f32(sw * scale) + nw) / f32(sw + nw))
+        out.append([(tid, float(f32(f32(w) * fscale))) for tid, w in fr] if fscale != 0.0 else [])
+    return out
+
+
+def compose_transforms(a, b, b_is_affine=False):
+    """ComposeTransforms (transform/transform-common.cc:132-166) on host float32 matrices; None for an empty matrix."""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    if b.shape[0] == 0 or a.shape[1] == 0:
+        return None
+    if a.shape[1] == b.shape[0]:
+        be = b
+    elif a.shape[1] == b.shape[0] + 1:
+        be = np.zeros((b.shape[0] + 1, b.shape[1] + (0 if b_is_affine else 1)), np.float32)
+        be[:b.shape[0], :b.shape[1]] = b
+        be[-1, -1] = 1.0
+    else:
+        raise KhError("ComposeTransforms: mismatched dimensions, a has %d columns and b has %d rows." % (a.shape[1], b.shape[0]))
+    return (a.astype(np.float64) @ be.astype(np.float64)).astype(np.float32)
+
+
+def transform_feats(trans, feats, out=None):
+    """featbin/transform-feats.cc:98-118 on the device: linear when the transform has feature-dim columns, affine (an
+    implicit 1.0 appended to the features) with one more; KhError otherwise.  trans, feats: 2-D float32 device tensors."""
+    rows, cols, dim = int(trans.shape[0]), int(trans.shape[1]), int(feats.shape[1])
+    if cols not in (dim, dim + 1):
+        raise KhError("Transform matrix has bad dimension %dx%d versus feat dim %d%s" % (
+            rows, cols, dim, " [perhaps the transform was created by compose-transforms, and you forgot the --b-is-affine option?]"
+            if cols == dim + 2 else ""))
+    if out is None:
+        out = torch.empty((feats.shape[0], rows), dtype=torch.float32, device=feats.device)
+    add_mat_mat(out, 1.0, feats, kNoTrans, trans[:, :dim], kTrans, 0.0)
+    if cols == dim + 1:
+        add_vec_to_rows(out, 1.0, trans[:, dim].contiguous())
+    return out

@@ -241,6 +241,17 @@ SIGNATURES = {
     "kh_align_compiled_set_workspace_limit": (C.c_int, [C.c_size_t]),
     "kh_align_compiled_set_lds_states": (C.c_int, [C.c_int]),
     "kh_align_compiled_last_timings": (C.c_int, [c_float_p, c_int32_p]),
+    "kh_gmm_component_posteriors": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, c_int32_p, C.c_int, c_int64_p, c_int32_p, c_float_p,
+                                              c_int64_p, vp, vp]),
+    "kh_fmllr_frame_stats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int,
+                                       c_int64_p, c_int32_p, c_int64_p, vp, c_int32_p, c_int32_p, vp, vp, vp]),
+    "kh_fmllr_accumulate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, vp, vp, vp, c_double_p, c_double_p, c_double_p]),
+    "kh_fmllr_update": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_char_p, C.c_float, C.c_int, C.c_int, c_float_p,
+                                  c_float_p, c_float_p]),
+    "kh_fmllr_set_workspace_limit": (C.c_int, [C.c_size_t]),
+    "kh_fmllr_max_dim": (C.c_int, []),
+    "kh_fmllr_frame_chunk": (C.c_int, []),
+    "kh_fmllr_last_timings": (C.c_int, [c_float_p]),
     "kh_lattice_forward_backward_mpe": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, c_int32_p, C.c_int, C.c_int, c_float_p, c_double_p, c_int32_p]),
     "kh_rescore_lattice": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, vp, C.c_int, c_int32_p, vp]),
     "kh_merge_pair_vector_summing": (C.c_int, [i64, c_int32_p, c_int32_p, c_float_p, i32, c_int32_p, c_int32_p, c_float_p, c_int64_p]),

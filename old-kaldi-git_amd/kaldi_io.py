@@ -384,6 +384,8 @@ def _read_object(s, binary, kind):
         return read_lattice_or_compact(s, binary)
     if kind == "posterior":
         return read_posterior(s, binary)
+    if kind == "gauss_post":
+        return read_gauss_post(s, binary)
     raise ValueError("unknown table object kind " + kind)
 
 
@@ -406,6 +408,8 @@ def _write_object(f, binary, kind, obj):
         write_compact_lattice(f, obj, binary)
     elif kind == "posterior":
         write_posterior(f, obj, binary)
+    elif kind == "gauss_post":
+        write_gauss_post(f, obj, binary)
     elif kind == "base_float":
         write_float(f, binary, obj)
         if not binary:
@@ -1285,6 +1289,34 @@ def read_posterior(s, binary=True):
         else:
             cur.append((int(tok[k]), float(tok[k + 1])))
             k += 2
+    return out
+
+
+def write_gauss_post(f, gpost, binary=True):
+    """GaussPostHolder::Write hmm/posterior.cc:141-164; gpost = per frame a list of (int32 pdf-id, float vector).  Not a
+    one-line format in text mode either: every vector ends its own line."""
+    write_int32(f, binary, len(gpost))
+    for frame in gpost:
+        write_int32(f, binary, len(frame))
+        for i, v in frame:
+            write_int32(f, binary, int(i))
+            write_vector(f, np.asarray(v, np.float32), binary)
+    if not binary:
+        f.write(b"\n")
+
+
+def read_gauss_post(s, binary=True):
+    """GaussPostHolder::Read hmm/posterior.cc:166-200."""
+    s = _as_stream(s)
+    n = read_int32(s, binary)
+    if n < 0:
+        raise ValueError("Reading posteriors: got negative size")
+    out = []
+    for _ in range(n):
+        m = read_int32(s, binary)
+        if m < 0:
+            raise ValueError("Reading posteriors: got negative size")
+        out.append([(read_int32(s, binary), np.asarray(read_vector(s, binary), np.float32)) for _ in range(m)])
     return out
 
 

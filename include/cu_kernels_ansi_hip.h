@@ -93,7 +93,8 @@ void cudaF_sum_column_ranges(KhDim3 Gr, KhDim3 Bl, float *data, MatrixDim dim, c
 void cudaF_matrix_lookup(KhDim3 Gr, KhDim3 Bl, const float *data, MatrixDim dim, const Int32Pair *indices,
                          int indices_size, float *output);
 /* :155 (cu-matrix.cc:1198-1248): x = s DEVICE elements; z = output, z2 = deriv;
- * t[0] += sum w log z(r,c), t[1] += sum w (DEVICE, 2 floats) */
+ * t[0] = sum w log z(r,c), t[1] = sum w (DEVICE, 2 floats; overwritten, as cu-kernels.cu:1031-1033 does;
+ * the caller adds them to its totals); z2(r,c) += w / z(r,c) */
 void cudaF_comp_obj_deriv(KhDim3 Gr, KhDim3 Bl, MatrixElementF *x, int s, const float *z, MatrixDim d, float *z2,
                           MatrixDim d2, float *t);
 /* legacy cuBLAS v1 SGEMM, column-major (cublas-wrappers.h:28-30; caller cu-matrix.cc:947-982) */

@@ -98,7 +98,11 @@ int kh_affine_pnorm_supported(int group_size);
 
 /* ------------------------------------------------------------------ a2
  * cudaF_softmax_reduce / CuMatrixBase::ApplySoftMaxPerRow cu-matrix.cc:1251-1271.
- * d describes y; x has stride src_stride. */
+ * d describes y; x has stride src_stride.
+ * In place (y == x with src_stride == d.stride) is supported, as with the reference's kernel, for both functions, every
+ * width and both element types: each kernel finishes a row's max and sum reductions before it stores to that row,
+ * and the store pass reads an element in the thread that then writes that index.  y and x that overlap in any other
+ * way are not. */
 int kh_softmax_per_row(float *y, const float *x, KhMatrixDim d, int src_stride);
 /* cudaF_log_softmax_reduce / ApplyLogSoftMaxPerRow cu-matrix.cc:1274-1295 */
 int kh_log_softmax_per_row(float *y, const float *x, KhMatrixDim d,

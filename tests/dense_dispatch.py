@@ -1,29 +1,34 @@
-"""Helpers of test_gpu_dense_dispatch.py.
+"""Helpers of test_gpu_dense_dispatch.py, test_gpu_double.py and test_gpu_cuda_seam.py.
 
 1. The launch conditions of the dense forward-path kernels restated as pure functions of shapes, strides and base
    pointers (each cites the source line it mirrors), so a test can assert that its operands land in the branch it is
    about BEFORE it calls the kernel: a case that drifts out of its branch (the allocator's alignment, a changed
    threshold) then fails loudly instead of passing on another path.
 2. NanView: an operand as a view into a NaN-filled buffer, with a chosen row stride (padding) and base offset (a
-   column offset of 1-3 floats, what a CuSubMatrix caller passes); after the call the padding must still be NaN."""
+   column offset of 1-3 elements, what a CuSubMatrix caller passes); after the call the padding must still be NaN.
+   float32 unless a dtype is given."""
 import numpy as np
 import torch
 
 NAN = float("nan")
 
 
-class NanView:
-    """rows x cols float32 device view with row stride `stride` starting `offset` floats into a NaN-filled buffer."""
+NP_DTYPE = {torch.float32: np.float32, torch.float64: np.float64}
 
-    def __init__(self, rows, cols, stride=None, offset=0, host=None):
+
+class NanView:
+    """rows x cols device view (float32, or `dtype`) with row stride `stride` starting `offset` elements into a
+    NaN-filled buffer."""
+
+    def __init__(self, rows, cols, stride=None, offset=0, host=None, dtype=torch.float32):
         stride = cols if stride is None else stride
         assert stride >= cols and offset >= 0
-        self.shape, self.stride, self.offset = (rows, cols), stride, offset
-        self.buf = torch.full((offset + rows * stride,), NAN, dtype=torch.float32, device="cuda")
+        self.shape, self.stride, self.offset, self.dtype = (rows, cols), stride, offset, dtype
+        self.buf = torch.full((offset + rows * stride,), NAN, dtype=dtype, device="cuda")
         self.t = self._view(self.buf)
         if host is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(host, np.float32)))
-        assert self.t.data_ptr() == self.buf.data_ptr() + 4 * offset
+            self.t.copy_(torch.from_numpy(np.ascontiguousarray(host, NP_DTYPE[dtype])))
+        assert self.t.data_ptr() == self.buf.data_ptr() + self.buf.element_size() * offset
         assert rows <= 1 or self.t.stride(0) == stride
 
     def _view(self, buf):
@@ -43,14 +48,14 @@ class NanView:
             (bad,) + self.shape + (self.stride, self.offset))
 
 
-def mat(host, pad=0, offset=0):
-    """Host matrix -> NanView with `pad` floats of row padding and a base offset of `offset` floats."""
-    host = np.ascontiguousarray(host, np.float32)
-    return NanView(host.shape[0], host.shape[1], host.shape[1] + pad, offset, host)
+def mat(host, pad=0, offset=0, dtype=torch.float32):
+    """Host matrix -> NanView with `pad` elements of row padding and a base offset of `offset` elements."""
+    host = np.ascontiguousarray(host, NP_DTYPE[dtype])
+    return NanView(host.shape[0], host.shape[1], host.shape[1] + pad, offset, host, dtype)
 
 
-def vec(host):
-    return torch.from_numpy(np.ascontiguousarray(host, np.float32)).cuda()
+def vec(host, dtype=torch.float32):
+    return torch.from_numpy(np.ascontiguousarray(host, NP_DTYPE[dtype])).cuda()
 
 
 def num_cus():
@@ -116,6 +121,14 @@ def output_layer_launch(n_mix, n_pdf, x_ptr_aligned=True):
     return d
 
 
+def softmax_kernel(cols):
+    """The kernel kh_softmax_per_row / kh_log_softmax_per_row launch (kh_elementwise.hip:436-446, :458-468) and, for the
+    block kernel, whether the row is held in LDS (:52)."""
+    if cols <= 1024:
+        return "SoftmaxWaveKernel"
+    return "SoftmaxKernel<%d>%s" % (512 if cols > 4096 else 256, "" if cols <= SOFTMAX_LDS_COLS else " uncached")
+
+
 def max_group(sizes):
     return int(np.max(sizes))   # > 4: the tail loop of emit(), kh_elementwise.hip:177-181
 
@@ -161,6 +174,26 @@ def wave_row_stride(rows):
     """NormalizeKernel / AddDiagMat2Kernel: one wave per row, 4 per block, at most NumCUs()*8 blocks
     (kh_elementwise.hip:535-536, :549-550): more rows than wave slots take the grid-stride loop (:335-336, :357-358)."""
     return rows > min(-(-rows // 4), num_cus() * 8) * 4
+
+
+# ---------------------------------------------------------------- kh_double.hip
+# LaunchMap (kh_double.hip:149-160) is LaunchMap2D (kh_elementwise.hip:244-252) line for line: 256 threads from 256
+# columns on and 64 below, gx = min(DivUp(cols, bx), 64), gy = rows cut to NumCUs()*16 / gx blocks (at least 1) and to
+# 65535; Map2DD (:143-146) walks the same two grid-stride loops as Map2D.  So the float predicates are the double ones.
+map_d_grid = map2d_grid
+map_d_strides = map2d_strides
+
+
+def add_diag_mat2_d_row_loop(rows):
+    """AddDiagMat2DKernel: one wave per row, 4 per block, at most NumCUs()*8 blocks (kh_double.hip:301): more rows than
+    wave slots take the grid-stride loop (:201)."""
+    return rows > min(-(-rows // 4), num_cus() * 8) * 4
+
+
+def lookup_d_loop(n):
+    """LookupDKernel: one pair per thread, 256 per block, at most NumCUs()*8 blocks (kh_double.hip:353): more pairs than
+    threads take the grid-stride loop (:213)."""
+    return n > min(-(-n // 256), num_cus() * 8) * 256
 
 
 # ---------------------------------------------------------------- references

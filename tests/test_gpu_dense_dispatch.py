@@ -271,6 +271,31 @@ def test_output_layer_branches(api, oracle, monkeypatch, case):
             cases.close(got, oracle.nnet_forward(comps, feats, True), rtol=1e-4, atol=1e-7)
 
 
+@pytest.mark.parametrize("cols,kernel", [(65, "SoftmaxWaveKernel"), (1024, "SoftmaxWaveKernel"), (1500, "SoftmaxKernel<256>"),
+                                         (5000, "SoftmaxKernel<512>"), (12500, "SoftmaxKernel<512> uncached")])
+def test_softmax_in_place(api, rng, cols, kernel):
+    """y == x (the guarantee stated in include/kaldi_hip.h) through each float softmax kernel: the wave kernel, the
+    block kernel at both block sizes with the row in LDS, and its uncached form that re-reads the row from memory in
+    all three passes.  5 rows (two blocks of the wave kernel).  Bit-identical to the out-of-place result, and held
+    to the project's 1e-5 relative (cases.RTOL; 5e-5 absolute for the logarithm, as the seam's test) against the
+    float64 value: the oracle sums a row sequentially in float32 and at 12500 columns is itself 8.6e-6 from it."""
+    X = (rng.standard_normal((5, cols)) * 3).astype(np.float32)
+    assert dd.softmax_kernel(cols) == kernel
+    z64 = X.astype(np.float64) - X.astype(np.float64).max(1, keepdims=True)
+    lse = np.log(np.exp(z64).sum(1, keepdims=True))
+    for fn, want, atol in ((api.apply_softmax_per_row, np.exp(z64 - lse), 1e-30),
+                           (api.apply_log_softmax_per_row, z64 - lse, 5e-5)):
+        x, y, z = dd.mat(X, 2, 1), dd.NanView(5, cols, cols + 3, 1), dd.mat(X, 2, 1)
+        fn(y.t, x.t)
+        fn(z.t, z.t)
+        got = z.host()
+        for v in (x, y, z):
+            v.assert_padding_untouched()
+        cases.exact(x.host(), X)
+        assert np.array_equal(got.view(np.int32), y.host().view(np.int32))
+        cases.close(got, want, rtol=cases.RTOL, atol=atol)
+
+
 def test_empty_column_ranges(api, oracle, rng):
     """Empty ranges (b == e) sum to exactly 0 in kh_sum_column_ranges, at the start, in the middle and at the end of
     the row.  A network cannot hold one: SumGroupComponent's sizes must be positive (kh_nnet.hip:249, as the

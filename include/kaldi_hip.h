@@ -925,6 +925,50 @@ int kh_compact_lattice_align_words(
 int kh_compact_lattice_align_words_set_workspace_limit(size_t bytes);
 int kh_compact_lattice_align_words_last_timings(float *ms6, int32_t *counts3);
 
+/* RescoreCompactLattice = RescoreCompactLatticeInternal(NULL, 1.0, ...) (lat/lattice-functions.cc:1163-1290; gmm-rescore-lattice,
+ * gmmbin/gmm-rescore-lattice.cc) with CompactLatticeStateTimes (:69-106) for a batch of top-sorted CompactLattices in one
+ * call (csrc/kh_latrescore.hip).  HOST CSR as kh_compact_lattice_align_words takes it (every arc to a higher-numbered state;
+ * the caller renumbers as fst::TopSort does, :1173-1178), with ONE transition-id array: arc a's string at
+ * strings[arc_string_offsets[a] .. [a + 1]), state s's final string at strings[final_string_offsets[s] .. [s + 1]), n_strings
+ * entries in all.  loglikes: DEVICE matrix of LogLikelihood(frame, pdf), lattice l's frames in rows ll_row_offsets[l] ..
+ * [l + 1]; tid2pdf: HOST, TransitionIdToPdf as num_tids + 1 entries indexed by transition-id (entry 0 unused), every value a
+ * column of the matrix.  arc_acoustic / final_acoustic: HOST, updated in place.
+ * status[l], utt_len[l] (HOST, always written), decided on the host before anything runs, the first that holds:
+ *   KH_RESCORE_EMPTY               no states or lat_start < 0 (:1169 "Rescoring empty lattice");
+ *   KH_RESCORE_INCONSISTENT_TIMES  lat_start != 0 (:72), two paths of different length into one state (the assertion at :87),
+ *                                  or a state that no path reaches (time -1, :1187);
+ *   KH_RESCORE_MISMATCH            a string that begins past utt_len (:1200-1204 "lattice/feature mismatch"), or one that
+ *                                  begins before utt_len and ends past it, where the reference writes past time_to_state;
+ *   KH_RESCORE_FEATURES_TOO_SHORT  fewer rows than utt_len (:1221-1225; the last frame the reference names is rows - 1);
+ *   KH_RESCORE_BAD_TID             a transition-id outside 1 .. num_tids in a string that would be looked up (the reference
+ *                                  indexes unchecked);
+ *   KH_RESCORE_OK                  rescored.  A row range longer than utt_len is fine.
+ * utt_len: :77-105 - the maximum of time + final string length over the final states when they disagree, 0 without a final
+ * state; 0 for EMPTY and INCONSISTENT_TIMES.  A lattice with another status than OK keeps every bit (the reference has by
+ * then updated the frames before the one it stops at, and its caller drops the lattice).
+ * THE ARITHMETIC.  The reference walks t ascending and adds -LogLikelihood(t, tid) to the weight that owns (t, tid) in
+ * place (:1270, :1283), so for an arc from a state of time t0 (or a non-Zero final weight there) with string s_0 .. s_{n-1}
+ *   v = old;  for k = 0 .. n-1:  v = fl32((-loglikes[row0 + t0 + k][tid2pdf[s_k]]) + v)
+ * strictly in that order; an empty string keeps its bits (a -0.0 too), and so does a string that begins at utt_len (:1196).
+ * One device work item per arc and per final weight with a string: a thread for strings of up to 8 transition-ids, a wave
+ * for longer ones (it gathers 64 frames at a time and folds them in string order) - the same sums either way.
+ * kh_rescore_compact_lattice_last_timings: milliseconds the last call of this thread spent in { host preparation (times,
+ * statuses, item lists), uploads, kernels, downloads (HIP events), the whole call by the host's clock }, and counts3 (may
+ * be NULL) = { kernel launches, items of the thread mapping, items of the wave mapping }. */
+#define KH_RESCORE_OK 0
+#define KH_RESCORE_EMPTY 1
+#define KH_RESCORE_INCONSISTENT_TIMES 2
+#define KH_RESCORE_FEATURES_TOO_SHORT 3
+#define KH_RESCORE_BAD_TID 4
+#define KH_RESCORE_MISMATCH 5
+int kh_rescore_compact_lattice(
+    int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start, const int64_t *arc_offsets,
+    const int32_t *arc_nextstate, float *arc_acoustic, const int64_t *arc_string_offsets, const float *final_graph,
+    float *final_acoustic, const int64_t *final_string_offsets, const int32_t *strings, int64_t n_strings,
+    const float *loglikes, KhMatrixDim d_loglikes, const int32_t *ll_row_offsets, int num_tids, const int32_t *tid2pdf,
+    int32_t *status, int32_t *utt_len);
+int kh_rescore_compact_lattice_last_timings(float *ms5, int32_t *counts3);
+
 /* Forced alignment of a batch of utterances, each against its own graph: FasterDecoder (decoder/faster-decoder.{h,cc}) as
  * AlignUtteranceWrapper drives it (decoder/decoder-wrappers.cc:456-482; gmm-align-compiled, nnet-align-compiled), with
  * max_active = INT_MAX.  One call = one Decode() per utterance with the given beam; the retry with a second beam is the

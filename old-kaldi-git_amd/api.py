@@ -2171,6 +2171,129 @@ def compact_lattice_align_words_last_timings():
                 launches=n[0], run_again=n[1], tuples=n[2])
 
 
+RESCORE_OK, RESCORE_EMPTY, RESCORE_INCONSISTENT_TIMES, RESCORE_FEATURES_TOO_SHORT, RESCORE_BAD_TID, RESCORE_MISMATCH = range(6)
+RESCORE_CYCLIC = 6      # compact_lattice_rescore's own: fst::TopSort failed ("Cycles detected in lattice."); never from the C call
+
+
+def compact_lattice_rescore_raw(csrs, loglikes, row_offsets, tid2pdf):
+    """kh_rescore_compact_lattice on CSR dicts (compact_lattice_align_csr: top-sorted, with the strings).  loglikes: DEVICE
+    frame x pdf matrix, lattice i's frames in rows row_offsets[i] .. [i + 1]; tid2pdf: num_tids + 1 entries indexed by
+    transition-id.  Returns (status [n] of RESCORE_*, utt_len [n], arc_acoustic, final_acoustic: per lattice the new float32
+    arrays in CSR order - the old bits where the status is not RESCORE_OK)."""
+    n = len(csrs)
+    if n == 0:
+        raise KhError("compact_lattice_rescore: no lattices")
+    if loglikes.dim() != 2 or loglikes.dtype != torch.float32 or not loglikes.is_cuda or loglikes.stride(1) != 1:
+        raise KhError("compact_lattice_rescore: loglikes must be a float32 device matrix with unit column stride")
+    soff = np.zeros(n + 1, np.int32)
+    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
+    aoff, base = [np.zeros(1, np.int64)], 0
+    for L in csrs:
+        o = np.asarray(L["arc_offsets"], np.int64)
+        aoff.append(o[1:] + base)
+        base += int(o[-1])
+    aoff = np.ascontiguousarray(np.concatenate(aoff))
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt).reshape(-1) for L in csrs] + [np.zeros(0, dt)]))
+    arc_strings = [x for L in csrs for x in L["arc_string"]]
+    final_strings = [x for L in csrs for x in L["final_string"]]
+    lens = lambda strs: np.asarray([len(x) for x in strs], np.int64)
+    aso = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens(arc_strings))]).astype(np.int64))
+    fso = np.ascontiguousarray((np.concatenate([[0], np.cumsum(lens(final_strings))]) + aso[-1]).astype(np.int64))
+    strings = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in arc_strings + final_strings] +
+                                                  [np.zeros(0, np.int32)]))
+    starts = np.ascontiguousarray(np.asarray([int(L.get("start", 0)) for L in csrs], np.int32))
+    ns, a, fg, fa = cat("arc_nextstate", np.int32), cat("arc_acoustic", np.float32), cat("final_graph", np.float32), cat("final_acoustic", np.float32)
+    a, fa = a.copy(), fa.copy()
+    t2p = np.ascontiguousarray(np.asarray(tid2pdf).astype(np.int32).reshape(-1))
+    rows = np.ascontiguousarray(np.asarray(row_offsets).astype(np.int32).reshape(-1))
+    if len(rows) != n + 1 or len(t2p) < 2:
+        raise KhError("compact_lattice_rescore: row_offsets needs one entry per lattice and one more; tid2pdf num_tids + 1")
+    status, utt_len = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ip, fp, lp = capi.c_int32_p, capi.c_float_p, capi.c_int64_p
+    ptr = lambda x, t: x.ctypes.data_as(t)
+    check(lib().kh_rescore_compact_lattice(
+        n, ptr(soff, ip), ptr(starts, ip), ptr(aoff, lp), ptr(ns, ip), ptr(a, fp), ptr(aso, lp), ptr(fg, fp), ptr(fa, fp),
+        ptr(fso, lp), ptr(strings, ip), len(strings), _p(loglikes), _dim(loglikes), ptr(rows, ip), len(t2p) - 1, ptr(t2p, ip),
+        ptr(status, ip), ptr(utt_len, ip)))
+    arcs = [a[int(aoff[soff[i]]):int(aoff[soff[i + 1]])].copy() for i in range(n)]
+    finals = [fa[int(soff[i]):int(soff[i + 1])].copy() for i in range(n)]
+    return status, utt_len, arcs, finals
+
+
+def compact_lattice_rescore(clats, loglikes, row_offsets, tid2pdf):
+    """RescoreCompactLattice (lat/lattice-functions.cc:1163-1290, 1297-1304) for a batch of CompactLattices (dicts of
+    kaldi_io.read_compact_lattice, with the strings) in ONE call; loglikes, row_offsets, tid2pdf as
+    compact_lattice_rescore_raw takes them.  Returns per lattice dict(status [RESCORE_*], utt_len, clat): clat = the rescored
+    lattice in the same dict layout and in the TOP-SORTED numbering - the reference sorts its argument in place (:1173-1178,
+    compact_lattice_top_order) and that is what gmm-rescore-lattice writes - or None where the status is not RESCORE_OK.
+    RESCORE_CYCLIC: the sort failed ("Cycles detected in lattice.")."""
+    csrs, cyclic = [], []
+    for c in clats:
+        try:
+            csrs.append(compact_lattice_align_csr(c))
+            cyclic.append(False)
+        except KhError as e:
+            if "cycles found" not in str(e):
+                raise
+            csrs.append(compact_lattice_align_csr(dict(n_states=0)))
+            cyclic.append(True)
+    status, utt_len, arcs, finals = compact_lattice_rescore_raw(csrs, loglikes, row_offsets, tid2pdf)
+    out = []
+    for i, L in enumerate(csrs):
+        if cyclic[i]:
+            out.append(dict(status=RESCORE_CYCLIC, utt_len=0, clat=None))
+            continue
+        c = None
+        if status[i] == RESCORE_OK:
+            n = int(L["n_states"])
+            c = dict(n_states=n, start=int(L["start"]),
+                     arc_src=np.repeat(np.arange(n, dtype=np.int32), np.diff(np.asarray(L["arc_offsets"], np.int64))),
+                     arc_dst=np.asarray(L["arc_nextstate"], np.int32).copy(), arc_label=np.asarray(L["arc_label"], np.int32).copy(),
+                     arc_g=np.asarray(L["arc_graph"], np.float32).copy(), arc_a=arcs[i], arc_string=list(L["arc_string"]),
+                     final_g=np.asarray(L["final_graph"], np.float32).copy(), final_a=finals[i],
+                     final_string=list(L["final_string"]), complete=True)
+        out.append(dict(status=int(status[i]), utt_len=int(utt_len[i]), clat=c))
+    return out
+
+
+def gmm_rescore_compact_lattices(am, feats, utt_row_offsets, clats, tid2pdf, batch_frames=0):
+    """gmm-rescore-lattice's inner call (gmmbin/gmm-rescore-lattice.cc:86-89) for a batch: DecodableAmDiagGmm is unscaled
+    and prunes at its default -1.0 (gmm/decodable-am-diag-gmm.h), so the scores are am.pdf_log_likelihoods(feats,
+    log_sum_exp_prune=-1.0) - the dense frame x pdf matrix, which the fused scorer fills faster than a list of the (frame,
+    pdf) pairs the lattices use could be built.  feats: DEVICE matrix, lattice i's frames in rows utt_row_offsets[i] ..
+    [i + 1].  batch_frames > 0 bounds that matrix: consecutive lattices are scored and rescored in groups of at most that
+    many frames (one lattice always runs).  Returns compact_lattice_rescore's list."""
+    n = len(clats)
+    rows = np.asarray(utt_row_offsets).astype(np.int64).reshape(-1)
+    if n == 0 or len(rows) != n + 1 or np.any(np.diff(rows) < 0) or rows[0] < 0 or rows[-1] > feats.shape[0]:
+        raise KhError("gmm_rescore_compact_lattices: utt_row_offsets needs one ascending entry per lattice and one more, within feats")
+    out, i = [], 0
+    while i < n:
+        j = i + 1
+        while j < n and batch_frames > 0 and rows[j + 1] - rows[i] <= batch_frames:
+            j += 1
+        if batch_frames <= 0:
+            j = n
+        r0, r1 = int(rows[i]), int(rows[j])
+        if r1 > r0:
+            ll = am.pdf_log_likelihoods(feats[r0:r1], log_sum_exp_prune=-1.0)
+        else:       # no frames at all: every lattice with a transition-id comes back RESCORE_FEATURES_TOO_SHORT
+            ll = torch.zeros((1, am.num_pdfs), dtype=torch.float32, device=feats.device)
+        out.extend(compact_lattice_rescore(clats[i:j], ll, rows[i:j + 1] - r0, tid2pdf))
+        i = j
+    return out
+
+
+def compact_lattice_rescore_last_timings():
+    """Milliseconds the last compact_lattice_rescore_raw call of this thread spent in host preparation / uploads / kernels /
+    downloads, in the whole C call, and the number of kernel launches and of items rescored one per thread and one per wave."""
+    ms = (C.c_float * 5)()
+    n = (C.c_int32 * 3)()
+    check(lib().kh_rescore_compact_lattice_last_timings(ms, n))
+    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n[0],
+                thread_items=n[1], wave_items=n[2])
+
+
 ALIGNC_DONE, ALIGNC_NO_FINAL, ALIGNC_NEEDS_ROOM, ALIGNC_TOO_LARGE, ALIGNC_BOUND, ALIGNC_BAD_INPUT = range(6)
 
 _libm = None

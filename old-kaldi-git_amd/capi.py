@@ -237,6 +237,8 @@ SIGNATURES = {
     "kh_compact_lattice_align_words": (C.c_int, [C.c_int, c_int32_p, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_int64_p, c_int32_p, c_float_p, c_float_p, c_int64_p, c_int32_p, C.c_int, c_int32_p, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_float_p, c_float_p, c_int32_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_int32_p, c_int32_p]),
     "kh_compact_lattice_align_words_set_workspace_limit": (C.c_int, [C.c_size_t]),
     "kh_compact_lattice_align_words_last_timings": (C.c_int, [c_float_p, c_int32_p]),
+    "kh_rescore_compact_lattice": (C.c_int, [C.c_int, c_int32_p, c_int32_p, c_int64_p, c_int32_p, c_float_p, c_int64_p, c_float_p, c_float_p, c_int64_p, c_int32_p, C.c_int64, vp, KhMatrixDim, c_int32_p, C.c_int, c_int32_p, c_int32_p, c_int32_p]),
+    "kh_rescore_compact_lattice_last_timings": (C.c_int, [c_float_p, c_int32_p]),
     "kh_align_compiled": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_int32_p, c_float_p, c_int32_p, c_float_p, C.c_int, c_int32_p, vp, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.c_float, c_int64_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_float_p, c_float_p]),
     "kh_align_compiled_set_workspace_limit": (C.c_int, [C.c_size_t]),
     "kh_align_compiled_set_lds_states": (C.c_int, [C.c_int]),

@@ -701,7 +701,7 @@ def read_kaldi_object(rxfilename, reader):
 # ---------------------------------------------------------------- tables
 class SequentialTableReader:
     """SequentialTableReader<Holder> (kaldi-table-inl.h:63-520): iterate (key, object) of an rspecifier.  `kind` names the
-    Holder ("matrix", "vector", "int32_vector", "lattice", "compact_lattice", "wave", "token_vector", "fst" = fst::VectorFstHolder)."""
+    Holder ("matrix", "vector", "int32_vector", "lattice", "compact_lattice", "compact_lattice_converted", "wave", "token_vector", "fst" = fst::VectorFstHolder)."""
 
     def __init__(self, rspecifier, kind="matrix"):
         self.kind = kind

@@ -376,6 +376,8 @@ def _read_object(s, binary, kind):
         return np.asarray([int(w) for w in line.split()], np.int32)
     if kind == "compact_lattice":
         return read_compact_lattice(s, binary)
+    if kind == "compact_lattice_converted":
+        return read_compact_lattice_converted(s, binary)
     if kind == "lattice":
         return read_lattice(s, binary)
     if kind == "any_lattice":
@@ -1243,6 +1245,130 @@ def read_any_lattice(s, binary=True):
     state-level lattice."""
     compact, L = read_lattice_or_compact(s, binary)
     return compact_lattice_to_lattice(L) if compact else L
+
+
+def _fst_dfs(n, start, off, nxt):
+    """fst::DfsVisit (fst/dfs-visit.h) from the start state, then from every still unvisited state in number order, a
+    state's arcs in order: (states in discovery order, states in finishing order, True when a back arc was met)."""
+    color = [0] * n          # white / grey / black
+    discover, finish, cyclic = [], [], False
+    for root in ([start] if 0 <= start < n else []) + list(range(n)):
+        if color[root]:
+            continue
+        color[root] = 1
+        discover.append(root)
+        stack = [(root, off[root])]
+        while stack:
+            s, k = stack[-1]
+            if k < off[s + 1]:
+                stack[-1] = (s, k + 1)
+                t = nxt[k]
+                if color[t] == 0:
+                    color[t] = 1
+                    discover.append(t)
+                    stack.append((t, off[t]))
+                elif color[t] == 1:
+                    cyclic = True
+            else:
+                color[s] = 2
+                finish.append(s)
+                stack.pop()
+    return discover, finish, cyclic
+
+
+def lattice_to_compact_lattice(L):
+    """ConvertLattice(Lattice -> CompactLattice, invert = true) fstext/lattice-utils-inl.h:33-87: Factor
+    (fstext/factor-inl.h:36-151) joins every chain of states that have one arc in, one arc out, no output label on the way
+    out and no final weight into one arc - its string the chain's non-zero input labels, its weight the Times of the
+    chain's weights (float32 sums in chain order), its word the first arc's output label; the states that stay are numbered
+    in the order Factor first meets them (sources in DfsVisit's discovery order, destinations as their arcs are written),
+    then fst::TopSort renumbers (reverse finishing order of a second DfsVisit; applied even to an input that is sorted
+    already).  Arcs keep the order of their source state; final weights get empty strings.  Takes the raw-lattice dict of
+    read_lattice / api.LatticeFasterDecoder.get_raw_lattice, returns read_compact_lattice's layout."""
+    n = int(L["num_states"]) if "num_states" in L else len(L["state_final"])
+    start = int(L.get("start", 0 if n else -1))
+    empty = dict(n_states=0, arc_src=np.zeros(0, np.int32), arc_dst=np.zeros(0, np.int32), arc_label=np.zeros(0, np.int32),
+                 arc_g=np.zeros(0, np.float32), arc_a=np.zeros(0, np.float32), arc_string=[], final_g=np.zeros(0, np.float32),
+                 final_a=np.zeros(0, np.float32), final_string=[], complete=True, start=-1)
+    if n == 0 or start < 0:       # factor-inl.h:77
+        return empty
+    src = np.asarray(L["arc_src"], np.int64)
+    by_src = np.argsort(src, kind="stable")
+    off = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]).astype(np.int64).tolist()
+    dst = np.asarray(L["arc_dst"], np.int64)[by_src].tolist()
+    il = np.asarray(L["arc_il"], np.int64)[by_src].tolist()
+    ol = np.asarray(L["arc_ol"], np.int64)[by_src].tolist()
+    g = np.asarray(L["arc_g"], np.float32)[by_src]
+    a = np.asarray(L["arc_a"], np.float32)[by_src]
+    if "state_final_graph" in L:
+        fg, fa = np.asarray(L["state_final_graph"], np.float32), np.asarray(L["state_final_acoustic"], np.float32)
+    else:                          # (the decoder's raw lattice: the final cost is the graph cost, write_lattice)
+        fg = np.asarray(L["state_final"], np.float32)
+        fa = np.where(fg == np.inf, np.float32(np.inf), np.float32(0.0)).astype(np.float32)
+    is_final = ~((fg == np.inf) & (fa == np.inf))
+    order, _, _ = _fst_dfs(n, start, off, dst)                       # :78-80
+    # GetStateProperties :37-64 -> the removal rule :96-98
+    n_in, has_olabel = [0] * n, [False] * n
+    for s in range(n):
+        for k in range(off[s], off[s + 1]):
+            n_in[dst[k]] += 1
+            if ol[k] != 0:
+                has_olabel[s] = True
+    remove = [s != start and n_in[s] == 1 and off[s + 1] - off[s] == 1 and not has_olabel[s] and not bool(is_final[s])
+              for s in range(n)]
+    mapping = [-1] * n
+    n_out = 0
+    o_src, o_dst, o_lab, o_g, o_a, o_str = [], [], [], [], [], []
+    for state in order:                                               # :109-142
+        if remove[state]:
+            continue
+        if mapping[state] < 0:
+            mapping[state] = n_out
+            n_out += 1
+        for k in range(off[state], off[state + 1]):
+            sym = [il[k]] if il[k] != 0 else []
+            wg, wa, nx, steps = g[k], a[k], dst[k], 0
+            while remove[nx]:
+                k2 = off[nx]
+                wg, wa = np.float32(wg + g[k2]), np.float32(wa + a[k2])   # Times :125
+                if il[k2] != 0:
+                    sym.append(il[k2])
+                nx = dst[k2]
+                steps += 1
+                if steps > n:
+                    raise ValueError("lattice_to_compact_lattice: a cycle of chain states")
+            if mapping[nx] < 0:
+                mapping[nx] = n_out
+                n_out += 1
+            o_src.append(mapping[state]); o_dst.append(mapping[nx]); o_lab.append(ol[k]); o_g.append(wg); o_a.append(wa)
+            o_str.append(np.asarray(sym, np.int32))
+    f_src, f_dst = np.asarray(o_src, np.int64), np.asarray(o_dst, np.int64)
+    f_fg, f_fa = np.full(n_out, np.inf, np.float32), np.full(n_out, np.inf, np.float32)
+    for s in range(n):
+        if not remove[s] and mapping[s] >= 0 and is_final[s]:
+            f_fg[mapping[s]], f_fa[mapping[s]] = fg[s], fa[s]
+    # TopSort(&ffst) lattice-utils-inl.h:54 (fst/topsort.h: left as it is when cyclic)
+    by = np.argsort(f_src, kind="stable")
+    foff = np.concatenate([[0], np.cumsum(np.bincount(f_src, minlength=n_out))]).astype(np.int64).tolist()
+    _, finish, cyclic = _fst_dfs(n_out, mapping[start], foff, f_dst[by].tolist())
+    new = np.arange(n_out, dtype=np.int64)
+    if not cyclic:
+        new[np.asarray(finish[::-1], np.int64)] = np.arange(n_out)
+    state_of = np.argsort(new)
+    perm = by[np.argsort(new[f_src[by]], kind="stable")]              # StateSort: states move, a state's arcs keep their order
+    return dict(n_states=n_out, arc_src=new[f_src[perm]].astype(np.int32), arc_dst=new[f_dst[perm]].astype(np.int32),
+                arc_label=np.asarray(o_lab, np.int32)[perm], arc_g=np.asarray(o_g, np.float32)[perm],
+                arc_a=np.asarray(o_a, np.float32)[perm], arc_string=[o_str[j] for j in perm], final_g=f_fg[state_of],
+                final_a=f_fa[state_of], final_string=[np.zeros(0, np.int32) for _ in range(n_out)], complete=True,
+                start=int(new[mapping[start]]))
+
+
+def read_compact_lattice_converted(s, binary=True):
+    """CompactLatticeHolder::Read (lat/kaldi-lattice.cc:310-392): a table of CompactLattices comes back as it is, a table of
+    Lattices converted by ConvertLattice (lattice_to_compact_lattice) - what gmm-rescore-lattice's reader makes of the
+    state-level table `gmm-latgen-faster --determinize-lattice=false` writes."""
+    compact, L = read_lattice_or_compact(s, binary)
+    return L if compact else lattice_to_compact_lattice(L)
 
 
 def write_posterior(f, post, binary=True):

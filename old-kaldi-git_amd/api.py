@@ -8,6 +8,7 @@ torch is used only as the owner of device memory (tensors -> data_ptr()) and of
 the HIP stream; no computation is done by torch and there is no fallback: every
 function raises KhError (the KALDI_ERR equivalent) if the library call fails.
 """
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -1339,25 +1340,92 @@ def compact_lattice_top_order(clat):
     return order
 
 
+def _clat_to_csr(clat, order):
+    """The CSR dict of a CompactLattice dict in the numbering order[old] = new (None = as it is), and the start state there."""
+    n = int(clat["n_states"])
+    src, dst = np.asarray(clat["arc_src"], np.int64), np.asarray(clat["arc_dst"], np.int64)
+    state_of = np.arange(n, dtype=np.int64)
+    start = int(clat.get("start", 0))
+    if order is not None:
+        src, dst = order[src], order[dst]
+        state_of = np.argsort(order)
+        start = int(order[start])
+    perm = np.argsort(src, kind="stable")
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(np.bincount(src, minlength=n))
+    L = dict(n_states=n, arc_offsets=off, arc_label=np.asarray(clat["arc_label"], np.int32)[perm],
+             arc_nextstate=dst[perm].astype(np.int32), arc_graph=np.asarray(clat["arc_g"], np.float32)[perm],
+             arc_acoustic=np.asarray(clat["arc_a"], np.float32)[perm],
+             final_graph=np.asarray(clat["final_g"], np.float32)[state_of],
+             final_acoustic=np.asarray(clat["final_a"], np.float32)[state_of], perm=perm, state_of=state_of)
+    return L, start
+
+
 def compact_lattice_to_csr(clat):
     """CompactLattice dict (kaldi_io.read_compact_lattice / determinize_lattice_pruned) -> the top-sorted CSR arrays of
     kh_compact_lattice_best_paths, renumbered by compact_lattice_top_order when needed.  perm[j] = the dict's arc behind
     CSR arc j, state_of[s] = the dict's state behind CSR state s."""
-    n = int(clat["n_states"])
-    src, dst = np.asarray(clat["arc_src"], np.int64), np.asarray(clat["arc_dst"], np.int64)
-    order = compact_lattice_top_order(clat)
-    state_of = np.arange(n, dtype=np.int64)
-    if order is not None:
-        src, dst = order[src], order[dst]
-        state_of = np.argsort(order)
-    perm = np.argsort(src, kind="stable")
-    off = np.zeros(n + 1, np.int64)
-    off[1:] = np.cumsum(np.bincount(src, minlength=n))
-    return dict(n_states=n, arc_offsets=off, arc_label=np.asarray(clat["arc_label"], np.int32)[perm],
-                arc_nextstate=dst[perm].astype(np.int32), arc_graph=np.asarray(clat["arc_g"], np.float32)[perm],
-                arc_acoustic=np.asarray(clat["arc_a"], np.float32)[perm],
-                final_graph=np.asarray(clat["final_g"], np.float32)[state_of],
-                final_acoustic=np.asarray(clat["final_a"], np.float32)[state_of], perm=perm, state_of=state_of)
+    return _clat_to_csr(clat, compact_lattice_top_order(clat))[0]
+
+
+# ---------------------------------------------------------------- what the batched compact-lattice calls share
+def _batch_csr(csrs):
+    """CSR dicts -> (soff [n + 1 int32: the first state of each lattice], aoff [states + 1 int64: the batch's arc offsets],
+    lat_arc_off [n + 1 int64: the first arc of each lattice], cat): cat(key, dtype) joins that array of every dict, flattened
+    (an empty array where there is nothing to join)."""
+    n = len(csrs)
+    soff = np.zeros(n + 1, np.int32)
+    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
+    aoff, lat_arc_off = [np.zeros(1, np.int64)], np.zeros(n + 1, np.int64)
+    for i, L in enumerate(csrs):
+        o = np.asarray(L["arc_offsets"], np.int64)
+        aoff.append(o[1:] + lat_arc_off[i])
+        lat_arc_off[i + 1] = lat_arc_off[i] + int(o[-1])
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt).reshape(-1) for L in csrs] + [np.zeros(0, dt)]))
+    return soff, np.ascontiguousarray(np.concatenate(aoff)), lat_arc_off, cat
+
+
+def _point_arrays(points):
+    """[(scale, penalty)] as score_point returns them -> (scales [K x 4 float64], penalties [K float32])."""
+    scales = np.ascontiguousarray(np.stack([np.asarray(s, np.float64).reshape(4) for s, _ in points]))
+    return scales, np.ascontiguousarray(np.asarray([p for _, p in points], np.float32))
+
+
+def _path_room(soff, K):
+    """Offsets of the room for one path per (lattice, point): a path has at most n_states - 1 arcs."""
+    room = np.repeat(np.maximum(np.diff(soff).astype(np.int64) - 1, 1), K)
+    poff = np.zeros(len(room) + 1, np.int64)
+    poff[1:] = np.cumsum(room)
+    return poff
+
+
+def _split_paths(parcs, poff, plen, n, K):
+    return [[parcs[poff[i * K + p]:poff[i * K + p] + max(int(plen[i * K + p]), 0)].copy() for p in range(K)] for i in range(n)]
+
+
+@contextlib.contextmanager
+def _workspace_limit(setter, nbytes):
+    """Bound the calling thread's workspace for the calls inside (None = leave the default), and set it back after."""
+    if nbytes is not None:
+        check(setter(int(nbytes)))
+    try:
+        yield
+    finally:
+        if nbytes is not None:
+            check(setter(0))
+
+
+def _timings(fn, names, count_names):
+    """A *_last_timings call as a dict: the float milliseconds under `names`, then the int32 counts under `count_names`."""
+    ms = (C.c_float * len(names))()
+    n = (C.c_int32 * len(count_names))()
+    check(fn(ms, n))
+    out = dict(zip(names, ms))
+    out.update(zip(count_names, n))
+    return out
+
+
+_MS5 = ("host_prep_ms", "upload_ms", "kernel_ms", "download_ms", "call_ms")
 
 
 def compact_lattice_best_paths_raw(csrs, points, workspace_limit=None):
@@ -1369,42 +1437,23 @@ def compact_lattice_best_paths_raw(csrs, points, workspace_limit=None):
     n, K = len(csrs), len(points)
     if n == 0 or K == 0:
         raise KhError("compact_lattice_best_paths: no lattices or no score points")
-    soff = np.zeros(n + 1, np.int32)
-    for i, L in enumerate(csrs):
-        soff[i + 1] = soff[i] + L["n_states"]
-    aoff = [np.zeros(1, np.int64)]
-    base = 0
-    for L in csrs:
-        o = np.asarray(L["arc_offsets"], np.int64)
-        aoff.append(o[1:] + base)
-        base += int(o[-1])
-    aoff = np.ascontiguousarray(np.concatenate(aoff))
-    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt) for L in csrs]))
+    soff, aoff, _, cat = _batch_csr(csrs)
     lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
     g, a = cat("arc_graph", np.float32), cat("arc_acoustic", np.float32)
     fg, fa = cat("final_graph", np.float32), cat("final_acoustic", np.float32)
-    scales = np.ascontiguousarray(np.stack([np.asarray(s, np.float64).reshape(4) for s, _ in points]))
-    pens = np.ascontiguousarray(np.asarray([p for _, p in points], np.float32))
-    room = np.repeat(np.maximum(np.diff(soff).astype(np.int64) - 1, 1), K)      # a path has at most n_states - 1 arcs
-    poff = np.zeros(n * K + 1, np.int64)
-    poff[1:] = np.cumsum(room)
+    scales, pens = _point_arrays(points)
+    poff = _path_room(soff, K)
     plen, pfin = np.empty(n * K, np.int32), np.empty(n * K, np.int32)
     parcs = np.empty(int(poff[-1]), np.int32)
     tg, ta = np.empty(n * K, np.float32), np.empty(n * K, np.float32)
     ip, fp = capi.c_int32_p, capi.c_float_p
-    if workspace_limit is not None:
-        check(lib().kh_compact_lattice_best_paths_set_workspace_limit(int(workspace_limit)))
-    try:
+    with _workspace_limit(lib().kh_compact_lattice_best_paths_set_workspace_limit, workspace_limit):
         check(lib().kh_compact_lattice_best_paths(
             n, soff.ctypes.data_as(ip), aoff.ctypes.data_as(capi.c_int64_p), lab.ctypes.data_as(ip), ns.ctypes.data_as(ip),
             g.ctypes.data_as(fp), a.ctypes.data_as(fp), fg.ctypes.data_as(fp), fa.ctypes.data_as(fp), K,
             scales.ctypes.data_as(capi.c_double_p), pens.ctypes.data_as(fp), plen.ctypes.data_as(ip), parcs.ctypes.data_as(ip),
             poff.ctypes.data_as(capi.c_int64_p), pfin.ctypes.data_as(ip), tg.ctypes.data_as(fp), ta.ctypes.data_as(fp)))
-    finally:
-        if workspace_limit is not None:
-            check(lib().kh_compact_lattice_best_paths_set_workspace_limit(0))
-    paths = [[parcs[poff[i * K + p]:poff[i * K + p] + max(int(plen[i * K + p]), 0)].copy() for p in range(K)] for i in range(n)]
-    return plen.reshape(n, K), paths, pfin.reshape(n, K), tg.reshape(n, K), ta.reshape(n, K)
+    return plen.reshape(n, K), _split_paths(parcs, poff, plen, n, K), pfin.reshape(n, K), tg.reshape(n, K), ta.reshape(n, K)
 
 
 def compact_lattice_best_paths(clats, points, workspace_limit=None):
@@ -1449,10 +1498,7 @@ def compact_lattice_best_paths_last_timings():
     """Milliseconds the last compact_lattice_best_paths call of this thread spent in host preparation / upload / kernels /
     download (the allocations and the host's scatter are in none of the four), in the whole C call, and the number of
     kernel launches it took."""
-    ms = (C.c_float * 5)()
-    n = C.c_int32()
-    check(lib().kh_compact_lattice_best_paths_last_timings(ms, C.byref(n)))
-    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
+    return _timings(lib().kh_compact_lattice_best_paths_last_timings, _MS5, ("launches",))
 
 
 # ---------------------------------------------------------------- pruning over score points (csrc/kh_latprune.hip)
@@ -1474,23 +1520,8 @@ def compact_lattice_prune_order(clat):
 
 def compact_lattice_to_prune_csr(clat):
     """compact_lattice_to_csr in compact_lattice_prune_order's numbering, plus start = the start state in that numbering."""
-    n = int(clat["n_states"])
-    src, dst = np.asarray(clat["arc_src"], np.int64), np.asarray(clat["arc_dst"], np.int64)
-    order = compact_lattice_prune_order(clat)
-    state_of = np.arange(n, dtype=np.int64)
-    start = int(clat.get("start", 0))
-    if order is not None:
-        src, dst = order[src], order[dst]
-        state_of = np.argsort(order)
-        start = int(order[start])
-    perm = np.argsort(src, kind="stable")
-    off = np.zeros(n + 1, np.int64)
-    off[1:] = np.cumsum(np.bincount(src, minlength=n))
-    return dict(n_states=n, start=start, arc_offsets=off, arc_label=np.asarray(clat["arc_label"], np.int32)[perm],
-                arc_nextstate=dst[perm].astype(np.int32), arc_graph=np.asarray(clat["arc_g"], np.float32)[perm],
-                arc_acoustic=np.asarray(clat["arc_a"], np.float32)[perm],
-                final_graph=np.asarray(clat["final_g"], np.float32)[state_of],
-                final_acoustic=np.asarray(clat["final_a"], np.float32)[state_of], perm=perm, state_of=state_of)
+    L, start = _clat_to_csr(clat, compact_lattice_prune_order(clat))
+    return dict(L, start=start)
 
 
 def _point_beams(beams, K):
@@ -1512,37 +1543,23 @@ def compact_lattice_prune_raw(csrs, starts, points, beams, workspace_limit=None)
     n, K = len(csrs), len(points)
     if n == 0 or K == 0:
         raise KhError("compact_lattice_prune: no lattices or no score points")
-    soff = np.zeros(n + 1, np.int32)
-    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
-    aoff, lat_arc_off = [np.zeros(1, np.int64)], np.zeros(n + 1, np.int64)
-    for i, L in enumerate(csrs):
-        o = np.asarray(L["arc_offsets"], np.int64)
-        aoff.append(o[1:] + lat_arc_off[i])
-        lat_arc_off[i + 1] = lat_arc_off[i] + int(o[-1])
-    aoff = np.ascontiguousarray(np.concatenate(aoff))
-    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt) for L in csrs]))
+    soff, aoff, lat_arc_off, cat = _batch_csr(csrs)
     lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
     g, a = cat("arc_graph", np.float32), cat("arc_acoustic", np.float32)
     fg, fa = cat("final_graph", np.float32), cat("final_acoustic", np.float32)
     st = np.ascontiguousarray(np.asarray(starts, np.int32).reshape(n))
-    scales = np.ascontiguousarray(np.stack([np.asarray(s, np.float64).reshape(4) for s, _ in points]))
-    pens = np.ascontiguousarray(np.asarray([p for _, p in points], np.float32))
+    scales, pens = _point_arrays(points)
     bm = _point_beams(beams, K)
     S, A, W = int(soff[-1]), int(lat_arc_off[-1]), (K + 63) // 64
     akeep, skeep, fkeep = np.zeros((A, W), np.uint64), np.zeros((S, W), np.uint64), np.zeros((S, W), np.uint64)
     best = np.empty((n, K), np.float64)
     ip, fp, up = capi.c_int32_p, capi.c_float_p, capi.c_uint64_p
-    if workspace_limit is not None:
-        check(lib().kh_compact_lattice_prune_set_workspace_limit(int(workspace_limit)))
-    try:
+    with _workspace_limit(lib().kh_compact_lattice_prune_set_workspace_limit, workspace_limit):
         check(lib().kh_compact_lattice_prune(
             n, soff.ctypes.data_as(ip), st.ctypes.data_as(ip), aoff.ctypes.data_as(capi.c_int64_p), lab.ctypes.data_as(ip),
             ns.ctypes.data_as(ip), g.ctypes.data_as(fp), a.ctypes.data_as(fp), fg.ctypes.data_as(fp), fa.ctypes.data_as(fp), K,
             scales.ctypes.data_as(capi.c_double_p), pens.ctypes.data_as(fp), bm.ctypes.data_as(fp), akeep.ctypes.data_as(up),
             skeep.ctypes.data_as(up), fkeep.ctypes.data_as(up), best.ctypes.data_as(capi.c_double_p)))
-    finally:
-        if workspace_limit is not None:
-            check(lib().kh_compact_lattice_prune_set_workspace_limit(0))
     # bit p % 64 of word p / 64 -> column p (the words are little-endian: byte p / 8, bit p % 8)
     bits = lambda m: np.unpackbits(m.astype("<u8").view(np.uint8).reshape(len(m), 8 * W), axis=1, bitorder="little")[:, :K].astype(bool)
     return dict(arc_keep=bits(akeep), state_keep=bits(skeep), final_keep=bits(fkeep), best_final_cost=best,
@@ -1634,10 +1651,7 @@ def compact_lattice_prune(clats, points, beams, workspace_limit=None):
 def compact_lattice_prune_last_timings():
     """Milliseconds the last compact_lattice_prune call of this thread spent in host preparation / upload / kernels /
     download (the allocations are in none of the four), in the whole C call, and the number of launches of the sweep kernel."""
-    ms = (C.c_float * 5)()
-    n = C.c_int32()
-    check(lib().kh_compact_lattice_prune_last_timings(ms, C.byref(n)))
-    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
+    return _timings(lib().kh_compact_lattice_prune_last_timings, _MS5, ("launches",))
 
 
 # ---------------------------------------------------------------- oracle path and depth (csrc/kh_latoracle.hip)
@@ -1671,15 +1685,7 @@ def compact_lattice_oracle_raw(csrs, starts, refs, wildcards, masks=None, worksp
     if n == 0 or len(refs) != n:
         raise KhError("compact_lattice_oracle: no lattices, or not one reference per lattice")
     K = 1 if masks is None else int(np.asarray(masks["final_keep"]).shape[1])
-    soff = np.zeros(n + 1, np.int32)
-    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
-    aoff, base = [np.zeros(1, np.int64)], 0
-    for L in csrs:
-        o = np.asarray(L["arc_offsets"], np.int64)
-        aoff.append(o[1:] + base)
-        base += int(o[-1])
-    aoff = np.ascontiguousarray(np.concatenate(aoff))
-    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt) for L in csrs]))
+    soff, aoff, _, cat = _batch_csr(csrs)
     lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
     fin = np.ascontiguousarray(np.concatenate([_csr_is_final(L) for L in csrs]).astype(np.int32))
     st = np.ascontiguousarray(np.asarray(starts, np.int32).reshape(n))
@@ -1700,25 +1706,18 @@ def compact_lattice_oracle_raw(csrs, starts, refs, wildcards, masks=None, worksp
         if not (len(ak) == len(lab) and len(sk) == len(fk) == int(soff[-1])):
             raise KhError("compact_lattice_oracle: the masks have %d, %d, %d rows for %d arcs and %d states"
                           % (len(ak), len(sk), len(fk), len(lab), int(soff[-1])))
-    room = np.repeat(np.maximum(np.diff(soff).astype(np.int64) - 1, 1), K)      # a path has at most n_states - 1 arcs
-    poff = np.zeros(n * K + 1, np.int64)
-    poff[1:] = np.cumsum(room)
+    poff = _path_room(soff, K)
     err, cnt = np.empty(n * K, np.int32), np.empty(n * K * 4, np.int32)
     plen, pfin = np.empty(n * K, np.int32), np.empty(n * K, np.int32)
     parcs = np.empty(int(poff[-1]), np.int32)
     fsum = np.zeros(n * K, np.int64)
-    if workspace_limit is not None:
-        check(lib().kh_compact_lattice_oracle_set_workspace_limit(int(workspace_limit)))
-    try:
+    with _workspace_limit(lib().kh_compact_lattice_oracle_set_workspace_limit, workspace_limit):
         check(lib().kh_compact_lattice_oracle(
             n, ptr(soff, ip), ptr(st, ip), ptr(aoff, lp), ptr(lab, ip), ptr(ns, ip), ptr(fin, ip), ptr(roff, lp), ptr(rw, ip),
             len(wild), ptr(wild, ip), K, ptr(ak, up), ptr(sk, up), ptr(fk, up), ptr(af, ip), ptr(ff, ip), ptr(err, ip),
             ptr(cnt, ip), ptr(plen, ip), ptr(parcs, ip), ptr(poff, lp), ptr(pfin, ip), ptr(fsum, lp) if frames else None))
-    finally:
-        if workspace_limit is not None:
-            check(lib().kh_compact_lattice_oracle_set_workspace_limit(0))
-    paths = [[parcs[poff[i * K + p]:poff[i * K + p] + max(int(plen[i * K + p]), 0)].copy() for p in range(K)] for i in range(n)]
-    return dict(errors=err.reshape(n, K), counts=cnt.reshape(n, K, 4), path_len=plen.reshape(n, K), paths=paths,
+    return dict(errors=err.reshape(n, K), counts=cnt.reshape(n, K, 4), path_len=plen.reshape(n, K),
+                paths=_split_paths(parcs, poff, plen, n, K),
                 final_state=pfin.reshape(n, K), frame_sum=fsum.reshape(n, K) if frames else None)
 
 
@@ -1838,10 +1837,7 @@ def compact_lattice_oracle(clats, refs, wildcards=(), points=None, beams=None, w
 def compact_lattice_oracle_last_timings():
     """Milliseconds the last compact_lattice_oracle call of this thread spent in host preparation / upload / kernel /
     download (the allocations are in none of the four), in the whole C call, and the number of kernel launches."""
-    ms = (C.c_float * 5)()
-    n = C.c_int32()
-    check(lib().kh_compact_lattice_oracle_last_timings(ms, C.byref(n)))
-    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n.value)
+    return _timings(lib().kh_compact_lattice_oracle_last_timings, _MS5, ("launches",))
 
 
 # ---------------------------------------------------------------- minimum Bayes risk decoding (csrc/kh_latmbr.hip)
@@ -1903,22 +1899,13 @@ def compact_lattice_mbr_raw(csrs, points, hyps, do_mbr=True, workspace_limit=Non
     n, K = len(csrs), len(points)
     if n == 0 or K == 0:
         raise KhError("compact_lattice_mbr: no lattices or no score points")
-    soff = np.zeros(n + 1, np.int32)
-    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
-    aoff, base = [np.zeros(1, np.int64)], 0
-    for L in csrs:
-        o = np.asarray(L["arc_offsets"], np.int64)
-        aoff.append(o[1:] + base)
-        base += int(o[-1])
-    aoff = np.ascontiguousarray(np.concatenate(aoff))
-    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt).reshape(-1) for L in csrs]))
+    soff, aoff, _, cat = _batch_csr(csrs)
     lab, ns = cat("arc_label", np.int32), cat("arc_nextstate", np.int32)
     g, a = cat("arc_graph", np.float32), cat("arc_acoustic", np.float32)
     fg, fa = cat("final_graph", np.float32), cat("final_acoustic", np.float32)
     times = cat("state_times", np.int32)
     st = np.ascontiguousarray(np.asarray([int(L.get("start", 0)) for L in csrs], np.int32))
-    scales = np.ascontiguousarray(np.stack([np.asarray(s, np.float64).reshape(4) for s, _ in points]))
-    pens = np.ascontiguousarray(np.asarray([p for _, p in points], np.float32))
+    scales, pens = _point_arrays(points)
     flat = [np.asarray(hyps[i][p], np.int32).reshape(-1) for i in range(n) for p in range(K)]
     hoff = np.zeros(n * K + 1, np.int64)
     hoff[1:] = np.cumsum([len(h) for h in flat])
@@ -1932,9 +1919,7 @@ def compact_lattice_mbr_raw(csrs, points, hyps, do_mbr=True, workspace_limit=Non
     ip, fp, lp, dp = capi.c_int32_p, capi.c_float_p, capi.c_int64_p, capi.c_double_p
     ptr = lambda x, t: x.ctypes.data_as(t)
     offs = lambda room: np.ascontiguousarray(np.concatenate([[0], np.cumsum(room)]).astype(np.int64))
-    if workspace_limit is not None:
-        check(lib().kh_compact_lattice_mbr_set_workspace_limit(int(workspace_limit)))
-    try:
+    with _workspace_limit(lib().kh_compact_lattice_mbr_set_workspace_limit, workspace_limit):
         for attempt in range(2):
             woff, boff, soff2 = offs(room_w), offs(room_b), offs(room_s)
             words, obt, obc = np.zeros(int(woff[-1]), np.int32), np.zeros(2 * int(woff[-1]), np.float32), np.zeros(int(woff[-1]), np.float32)
@@ -1950,9 +1935,6 @@ def compact_lattice_mbr_raw(csrs, points, hyps, do_mbr=True, workspace_limit=Non
                 continue
             check(rc)
             break
-    finally:
-        if workspace_limit is not None:
-            check(lib().kh_compact_lattice_mbr_set_workspace_limit(0))
     out = []
     for i in range(n):
         row = []
@@ -2010,11 +1992,7 @@ def compact_lattice_mbr_last_timings():
     """Milliseconds the last compact_lattice_mbr_raw call of this thread spent in host preparation (alpha and the arc
     posteriors among it) / uploads / kernels / downloads, in the whole C call, in the host's part of MbrDecode, and the
     number of kernel launches, rounds of the host loop, and AccStats() calls summed over the (lattice, point) pairs."""
-    ms = (C.c_float * 6)()
-    n = (C.c_int32 * 3)()
-    check(lib().kh_compact_lattice_mbr_last_timings(ms, n))
-    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], host_loop_ms=ms[5],
-                launches=n[0], rounds=n[1], acc_stats=n[2])
+    return _timings(lib().kh_compact_lattice_mbr_last_timings, _MS5 + ("host_loop_ms",), ("launches", "rounds", "acc_stats"))
 
 
 ALIGN_OK, ALIGN_ERROR, ALIGN_EMPTY, ALIGN_TOO_MANY_STATES, ALIGN_FATAL = range(5)
@@ -2040,14 +2018,7 @@ def compact_lattice_align_csr(clat):
 def compact_lattice_align_words_pack(csrs, tmodel, wbinfo, max_states=0):
     """The arguments of kh_compact_lattice_align_words as contiguous arrays: a dict in the C call's order of names."""
     n = len(csrs)
-    soff = np.zeros(n + 1, np.int32)
-    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
-    aoff, base = [np.zeros(1, np.int64)], 0
-    for L in csrs:
-        o = np.asarray(L["arc_offsets"], np.int64)
-        aoff.append(o[1:] + base)
-        base += int(o[-1])
-    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt).reshape(-1) for L in csrs] + [np.zeros(0, dt)]))
+    soff, aoff, _, cat = _batch_csr(csrs)
     arc_strings = [x for L in csrs for x in L["arc_string"]]
     final_strings = [x for L in csrs for x in L["final_string"]]
     offs = lambda strs: np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(x) for x in strs])]).astype(np.int64))
@@ -2057,7 +2028,7 @@ def compact_lattice_align_words_pack(csrs, tmodel, wbinfo, max_states=0):
     if np.any(ms < 0) or np.any(ms >= 2 ** 31):
         raise KhError("compact_lattice_align_words: max_states out of range")
     return dict(lat_state_offsets=soff, lat_start=i32([int(L.get("start", 0)) for L in csrs]),
-                arc_offsets=np.ascontiguousarray(np.concatenate(aoff)), arc_label=cat("arc_label", np.int32),
+                arc_offsets=aoff, arc_label=cat("arc_label", np.int32),
                 arc_nextstate=cat("arc_nextstate", np.int32), arc_graph=cat("arc_graph", np.float32),
                 arc_acoustic=cat("arc_acoustic", np.float32), arc_string_offsets=offs(arc_strings), arc_strings=flat(arc_strings),
                 final_graph=cat("final_graph", np.float32), final_acoustic=cat("final_acoustic", np.float32),
@@ -2114,17 +2085,12 @@ def compact_lattice_align_words_raw(csrs, tmodel, wbinfo, max_states=0, workspac
         rooms = [2 * arcs + 4, 2 * arcs + 4, 2 * words + 4]
     else:
         rooms = [np.asarray(r, np.int64).reshape(n) for r in room]
-    if workspace_limit is not None:
-        check(lib().kh_compact_lattice_align_words_set_workspace_limit(int(workspace_limit)))
-    try:
+    with _workspace_limit(lib().kh_compact_lattice_align_words_set_workspace_limit, workspace_limit):
         rc, cnt, O = compact_lattice_align_words_call(A, *rooms)
         need = [cnt["n_states"].astype(np.int64), cnt["n_arcs"].astype(np.int64), cnt["n_string_words"].astype(np.int64)]
         if rc != 0 and room is None and any(np.any(x > r) for x, r in zip(need, rooms)):   # the counts are always written
             rc, cnt, O = compact_lattice_align_words_call(A, *need)
         check(rc)
-    finally:
-        if workspace_limit is not None:
-            check(lib().kh_compact_lattice_align_words_set_workspace_limit(0))
     so, ao, wo, alen, strs = O["state_offsets"], O["arc_offsets"], O["string_offsets"], O["arc_string_len"], O["strings"]
     out = []
     for i in range(n):
@@ -2164,11 +2130,8 @@ def compact_lattice_align_words_last_timings():
     """Milliseconds the last compact_lattice_align_words_raw call of this thread spent in host preparation / uploads / kernels
     / downloads, in the whole C call, in the host's sort and merge, and the number of kernel launches, of lattices run again
     with more room, and of tuples over all lattices."""
-    ms = (C.c_float * 6)()
-    n = (C.c_int32 * 3)()
-    check(lib().kh_compact_lattice_align_words_last_timings(ms, n))
-    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], host_finish_ms=ms[5],
-                launches=n[0], run_again=n[1], tuples=n[2])
+    return _timings(lib().kh_compact_lattice_align_words_last_timings, _MS5 + ("host_finish_ms",),
+                    ("launches", "run_again", "tuples"))
 
 
 RESCORE_OK, RESCORE_EMPTY, RESCORE_INCONSISTENT_TIMES, RESCORE_FEATURES_TOO_SHORT, RESCORE_BAD_TID, RESCORE_MISMATCH = range(6)
@@ -2185,15 +2148,7 @@ def compact_lattice_rescore_raw(csrs, loglikes, row_offsets, tid2pdf):
         raise KhError("compact_lattice_rescore: no lattices")
     if loglikes.dim() != 2 or loglikes.dtype != torch.float32 or not loglikes.is_cuda or loglikes.stride(1) != 1:
         raise KhError("compact_lattice_rescore: loglikes must be a float32 device matrix with unit column stride")
-    soff = np.zeros(n + 1, np.int32)
-    soff[1:] = np.cumsum([int(L["n_states"]) for L in csrs])
-    aoff, base = [np.zeros(1, np.int64)], 0
-    for L in csrs:
-        o = np.asarray(L["arc_offsets"], np.int64)
-        aoff.append(o[1:] + base)
-        base += int(o[-1])
-    aoff = np.ascontiguousarray(np.concatenate(aoff))
-    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(L[k], dt).reshape(-1) for L in csrs] + [np.zeros(0, dt)]))
+    soff, aoff, _, cat = _batch_csr(csrs)
     arc_strings = [x for L in csrs for x in L["arc_string"]]
     final_strings = [x for L in csrs for x in L["final_string"]]
     lens = lambda strs: np.asarray([len(x) for x in strs], np.int64)
@@ -2287,11 +2242,7 @@ def gmm_rescore_compact_lattices(am, feats, utt_row_offsets, clats, tid2pdf, bat
 def compact_lattice_rescore_last_timings():
     """Milliseconds the last compact_lattice_rescore_raw call of this thread spent in host preparation / uploads / kernels /
     downloads, in the whole C call, and the number of kernel launches and of items rescored one per thread and one per wave."""
-    ms = (C.c_float * 5)()
-    n = (C.c_int32 * 3)()
-    check(lib().kh_rescore_compact_lattice_last_timings(ms, n))
-    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n[0],
-                thread_items=n[1], wave_items=n[2])
+    return _timings(lib().kh_rescore_compact_lattice_last_timings, _MS5, ("launches", "thread_items", "wave_items"))
 
 
 ALIGNC_DONE, ALIGNC_NO_FINAL, ALIGNC_NEEDS_ROOM, ALIGNC_TOO_LARGE, ALIGNC_BOUND, ALIGNC_BAD_INPUT = range(6)
@@ -2469,9 +2420,7 @@ def align_compiled_raw(graphs, loglikes, row_offsets, tid2pdf, beam, min_active=
     ro = np.asarray(row_offsets, np.int64).reshape(-1)
     frames = np.diff(ro)
     room = 2 * frames + 16 if path_room is None else np.broadcast_to(np.asarray(path_room, np.int64), (n,))
-    if workspace_limit is not None:
-        check(lib().kh_align_compiled_set_workspace_limit(int(workspace_limit)))
-    try:
+    with _workspace_limit(lib().kh_align_compiled_set_workspace_limit, workspace_limit):
         out = [None] * n
         todo = list(range(n))
         for attempt in range(2):
@@ -2498,9 +2447,6 @@ def align_compiled_raw(graphs, loglikes, row_offsets, tid2pdf, beam, min_active=
             todo = again
             if not todo:
                 break
-    finally:
-        if workspace_limit is not None:
-            check(lib().kh_align_compiled_set_workspace_limit(0))
     return out
 
 
@@ -2561,11 +2507,7 @@ def align_compiled_last_timings():
     """Milliseconds the last kh_align_compiled call of this thread spent in host preparation / uploads / kernels / downloads
     and in the whole call, and the number of kernel launches, of utterances whose costs lay in the workspace and of
     utterances launched."""
-    ms = (C.c_float * 5)()
-    n = (C.c_int32 * 3)()
-    check(lib().kh_align_compiled_last_timings(ms, n))
-    return dict(host_prep_ms=ms[0], upload_ms=ms[1], kernel_ms=ms[2], download_ms=ms[3], call_ms=ms[4], launches=n[0],
-                workspace_cost_utts=n[1], utts_launched=n[2])
+    return _timings(lib().kh_align_compiled_last_timings, _MS5, ("launches", "workspace_cost_utts", "utts_launched"))
 
 
 def rescore_lattice(lats, loglikes, utt_row_offsets, tid2pdf=None):

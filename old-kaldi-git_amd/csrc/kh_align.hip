@@ -34,13 +34,13 @@
 // lane, then __syncthreads()" on the device and "for every lane in turn" on the host, so a stand-alone host program steps
 // the same code with any lane count up to 256 (tools/align_host_step.cc).
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
 #include <numeric>
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_latbatch.h"
 
 namespace kh {
 namespace align {
@@ -539,30 +539,9 @@ inline int Prepare(int n_utts, const int32_t *state_offsets, const int64_t *arc_
 }
 
 #if !defined(KH_ALIGN_BODY_ONLY)
-thread_local float g_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-thread_local int32_t g_counts[3] = {0, 0, 0};   // launches, utterances whose costs lay in the workspace, utterances launched
-thread_local size_t g_workspace_limit = 0;
+static thread_local CallStats<5, 3> g_stats;   // counts: launches, utterances whose costs lay in the workspace, utterances launched
 thread_local int32_t g_lds_states = 3584;       // 2 x 8 x 3584 = 56 KiB of the 64 KiB a workgroup may ask for
 constexpr int32_t kMaxLdsStates = 3584;
-
-template <typename T>
-struct Dev {
-  T *p = nullptr;
-  size_t n = 0;
-  ~Dev() { if (p) PoolFree(p); }
-  int Alloc(size_t count) {
-    if (p) PoolFree(p);
-    n = count;
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * (count ? count : 1)));
-    return p ? KH_OK : KH_ENOMEM;
-  }
-  int Grow(size_t count) { return p && count <= n ? KH_OK : Alloc(count); }
-  int Upload(const std::vector<T> &h, hipStream_t st) {
-    if (Alloc(h.size())) return KH_ENOMEM;
-    if (!h.empty() && hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return KH_EDEVICE;
-    return KH_OK;
-  }
-};
 
 inline size_t BpWords(const Job &J) { return (static_cast<size_t>(J.T) + 1) * static_cast<size_t>(J.S); }
 inline size_t WorkspaceBytes(const Job &J, bool lds) {
@@ -578,7 +557,7 @@ using namespace kh;
 using namespace kh::align;
 
 extern "C" int kh_align_compiled_set_workspace_limit(size_t bytes) {
-  g_workspace_limit = bytes;
+  g_stats.workspace_limit = bytes;
   return KH_OK;
 }
 
@@ -589,10 +568,7 @@ extern "C" int kh_align_compiled_set_lds_states(int max_states) {
 }
 
 extern "C" int kh_align_compiled_last_timings(float *ms5, int32_t *counts3) {
-  KH_CHECK_ARG(ms5);
-  for (int i = 0; i < 5; i++) ms5[i] = g_ms[i];
-  if (counts3) for (int i = 0; i < 3; i++) counts3[i] = g_counts[i];
-  return KH_OK;
+  return GetTimings(g_stats, ms5, counts3);
 }
 
 extern "C" int kh_align_compiled(int n_utts, const int32_t *state_offsets, const int64_t *arc_offsets, const int32_t *start,
@@ -608,32 +584,25 @@ extern "C" int kh_align_compiled(int n_utts, const int32_t *state_offsets, const
                n_tid > 0 && loglikes && ll_rows >= 0 && ll_cols > 0 && ll_stride >= ll_cols && utt_row_offsets && path_offsets &&
                status && total_cost && best_state && path_len && path_ilabel && path_olabel && path_graph && path_acoustic);
   KH_CHECK_ARG(beam > 0.f && min_active >= 0 && beam_delta >= 0.f && !std::isnan(beam) && !std::isnan(beam_delta));
-  const auto t0 = std::chrono::steady_clock::now();
+  CallTimer T;
   Prepared P;
   std::string first_bad;
   if ((rc = Prepare(n_utts, state_offsets, arc_offsets, start, ilabel, weight, nextstate, final_w, n_tid, tid2pdf, ll_rows,
                     ll_cols, utt_row_offsets, path_offsets, &P, &first_bad)) != KH_OK)
     return rc;
-  const auto t1 = std::chrono::steady_clock::now();
+  T.HostDone();
   for (int u = 0; u < n_utts; u++) {
     status[u] = P.status[u];
     total_cost[u] = std::numeric_limits<double>::infinity();
     path_len[u] = 0;
     best_state[u] = -1;
   }
-  float ms_up = 0.f, ms_kernel = 0.f, ms_down = 0.f, ms = 0.f;
   int32_t n_launches = 0, n_ws_cost = 0, n_run = 0;
   if (!P.jobs.empty()) {
     hipStream_t st = Stream();
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    for (int i = 0; i < 4; i++) KH_HIP(hipEventCreate(&ev[i]));
-    size_t limit = g_workspace_limit;
-    if (limit == 0) {
-      size_t free_b = 0, total_b = 0;
-      if ((rc = kh_mem_info(&free_b, &total_b)) != KH_OK) return rc;
-      limit = (free_b + PoolCachedBytes()) / 2;
-    }
+    KH_HIP(T.Init());
+    size_t limit = g_stats.workspace_limit;   // by default half of what is free now, before the fixed buffers
+    if (limit == 0 && (rc = DefaultWorkspaceLimit(0, &limit)) != KH_OK) return rc;
     Dev<int32_t> d_e_off, d_n_off, d_path_arc, d_hdr;
     Dev<EArc> d_e;
     Dev<NArc> d_n;
@@ -644,15 +613,15 @@ extern "C" int kh_align_compiled(int n_utts, const int32_t *state_offsets, const
     Dev<Job> d_jobs;
     const size_t path_room = static_cast<size_t>(path_offsets[n_utts]);
     const std::vector<float> fin(final_w, final_w + state_offsets[n_utts]);
-    KH_HIP(hipEventRecord(ev[0], st));
+    KH_HIP(T.Mark(0, st));
     if (d_e_off.Upload(P.e_off, st) || d_e.Upload(P.e, st) || d_n_off.Upload(P.n_off, st) || d_n.Upload(P.n, st) ||
         d_arc.Upload(P.arc, st) || d_fin.Upload(fin, st) || d_path_arc.Alloc(path_room) || d_path_ac.Alloc(path_room)) {
       SetError("kh_align_compiled: out of device memory");
       return KH_ENOMEM;
     }
-    KH_HIP(hipEventRecord(ev[1], st));
+    KH_HIP(T.Mark(1, st));
     KH_HIP(hipStreamSynchronize(st));
-    KH_HIP(hipEventElapsedTime(&ms_up, ev[0], ev[1]));
+    KH_HIP(T.Add(&T.up, 0, 1));
     // what can run at all; largest workspace first, as many per launch as the limit admits
     std::vector<int32_t> todo;
     for (size_t j = 0; j < P.jobs.size(); j++) {
@@ -699,12 +668,12 @@ extern "C" int kh_align_compiled(int n_utts, const int32_t *state_offsets, const
       Ctx X{d_e_off.p, d_e.p, d_n_off.p, d_n.p, d_fin.p, d_arc.p, loglikes, static_cast<int64_t>(ll_stride), beam, beam_delta,
             min_active, reinterpret_cast<int32_t *>(d_ws.p), reinterpret_cast<double *>(d_ws.p), d_hdr.p, d_hdr_cost.p,
             d_path_arc.p, d_path_ac.p};
-      KH_HIP(hipEventRecord(ev[0], st));
-      KH_HIP(hipMemcpyAsync(d_jobs.p, batch.data(), sizeof(Job) * batch.size(), hipMemcpyHostToDevice, st));
-      KH_HIP(hipEventRecord(ev[1], st));
+      KH_HIP(T.Mark(0, st));
+      KH_HIP(Up(d_jobs, batch.data(), batch.size(), st));
+      KH_HIP(T.Mark(1, st));
       hipLaunchKernelGGL(AlignKernel, dim3(static_cast<unsigned>(batch.size())), dim3(kLanes), lds_bytes, st, d_jobs.p, X);
       KH_LAUNCH_CHECK();
-      KH_HIP(hipEventRecord(ev[2], st));
+      KH_HIP(T.Mark(2, st));
       h_hdr.resize(kHdr * batch.size());
       h_cost.resize(batch.size());
       KH_HIP(hipMemcpyAsync(h_hdr.data(), d_hdr.p, sizeof(int32_t) * h_hdr.size(), hipMemcpyDeviceToHost, st));
@@ -743,24 +712,19 @@ extern "C" int kh_align_compiled(int n_utts, const int32_t *state_offsets, const
           }
         }
       }
-      KH_HIP(hipEventRecord(ev[3], st));
+      KH_HIP(T.Mark(3, st));
       KH_HIP(hipStreamSynchronize(st));
-      KH_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      ms_up += ms;
-      KH_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-      ms_kernel += ms;
-      KH_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-      ms_down += ms;
+      KH_HIP(T.AddAll());
       n_launches++;
       n_run += static_cast<int32_t>(batch.size());
       i = e;
     }
   }
   if (!first_bad.empty()) SetError("%s", first_bad.c_str());
-  g_ms[0] = static_cast<float>(std::chrono::duration<double, std::milli>(t1 - t0).count());
-  g_ms[1] = ms_up; g_ms[2] = ms_kernel; g_ms[3] = ms_down;
-  g_ms[4] = static_cast<float>(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  g_counts[0] = n_launches; g_counts[1] = n_ws_cost; g_counts[2] = n_run;
+  T.Finish(g_stats.ms);
+  g_stats.counts[0] = n_launches;
+  g_stats.counts[1] = n_ws_cost;
+  g_stats.counts[2] = n_run;
   return KH_OK;
 }
 #endif  // KH_ALIGN_BODY_ONLY

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_devbuf.h"
 
 using namespace kh;
 
@@ -196,18 +197,6 @@ CmvnStatsKernel(const float *__restrict__ x, int rows, int cols, int stride, dou
   atomicAdd(&stats[cols + 1 + d], s2);
 }
 
-template <class T>
-struct Dev {
-  T *p = nullptr;
-  ~Dev() { if (p) PoolFree(p); }
-  int Up(const T *h, size_t n, hipStream_t st) {
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * (n ? n : 1)));
-    if (!p) return KH_ENOMEM;
-    if (n) KH_HIP(hipMemcpyAsync(p, h, sizeof(T) * n, hipMemcpyHostToDevice, st));
-    return KH_OK;
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -257,12 +246,12 @@ int kh_mfcc_compute_opts(const float *wave, int n_samples, int frame_shift, int 
   Dev<float> d_win, d_w, d_dct, d_lift;
   Dev<double> d_ct, d_st;
   Dev<int32_t> d_first, d_off;
-  if ((rc = d_win.Up(window_host, frame_length, st)) || (rc = d_ct.Up(ct.data(), padded, st)) ||
-      (rc = d_st.Up(st_.data(), padded, st)) || (rc = d_w.Up(mel_weights_host, mel_off_host[num_bins], st)) ||
-      (rc = d_dct.Up(dct_host, static_cast<size_t>(num_ceps) * num_bins, st)) ||
-      (rc = d_first.Up(mel_first_host, num_bins, st)) || (rc = d_off.Up(mel_off_host, num_bins + 1, st)))
+  if ((rc = d_win.Upload(window_host, frame_length, st)) || (rc = d_ct.Upload(ct.data(), padded, st)) ||
+      (rc = d_st.Upload(st_.data(), padded, st)) || (rc = d_w.Upload(mel_weights_host, mel_off_host[num_bins], st)) ||
+      (rc = d_dct.Upload(dct_host, static_cast<size_t>(num_ceps) * num_bins, st)) ||
+      (rc = d_first.Upload(mel_first_host, num_bins, st)) || (rc = d_off.Upload(mel_off_host, num_bins + 1, st)))
     return rc;
-  if (lifter_host && (rc = d_lift.Up(lifter_host, num_ceps, st))) return rc;
+  if (lifter_host && (rc = d_lift.Upload(lifter_host, num_ceps, st))) return rc;
   hipLaunchKernelGGL(MfccKernel, dim3(rows), dim3(kThreads), 0, st, wave, frame_shift, frame_length, padded,
                      preemph_coeff, remove_dc_offset, d_win.p, d_ct.p, d_st.p, num_bins, d_first.p, d_off.p, d_w.p,
                      num_ceps, d_dct.p, lifter_host ? d_lift.p : nullptr, out, out_stride, n_samples, opt);
@@ -282,7 +271,7 @@ int kh_compute_deltas(const float *in, KhMatrixDim d_in, int order, const float 
   hipStream_t st = Stream();
   Dev<float> d_sc;
   Dev<int32_t> d_len;
-  if ((rc = d_sc.Up(scales_host, n, st)) || (rc = d_len.Up(lens_host, order + 1, st))) return rc;
+  if ((rc = d_sc.Upload(scales_host, n, st)) || (rc = d_len.Upload(lens_host, order + 1, st))) return rc;
   const int out_cols = d_in.cols * (order + 1);
   hipLaunchKernelGGL(DeltasKernel, dim3((out_cols + 63) / 64, std::min(d_in.rows, NumCUs() * 32)), dim3(64), 0, st, in,
                      d_in.rows, d_in.cols, d_in.stride, order, d_sc.p, d_len.p, out, out_stride);

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_latbatch.h"
 
 namespace kh {
 namespace latalign {
@@ -323,13 +324,10 @@ __host__ __device__ inline void Classify(const AlignCtx &X, const AlignJob &J, i
 #undef KH_SELF
 }
 
+// WaveFence(): the tables are written by one lane and read by the others of the same wave later in program order.  The
+// device pass takes kh::WaveFence (kh_latbatch.h); on the host pass the stub below, declared in this inner namespace,
+// hides that __device__ function for AlignBody, which a host program steps through with one lane.
 #if defined(__HIP_DEVICE_COMPILE__)
-// the tables are written by one lane and read by the others of the same wave later in program order
-__device__ __forceinline__ void WaveFence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ unsigned long long Ballot(bool p) { return __ballot(p); }
 __device__ __forceinline__ int32_t FromLane(int32_t v, int l) { return __shfl(v, l); }
 __device__ __forceinline__ int FirstBit(unsigned long long m) { return __ffsll(static_cast<long long>(m)) - 1; }
@@ -744,28 +742,8 @@ void Finish(const Prepared &P, const AlignJob &J, const int32_t *hdr, const int3
   }
 }
 
-thread_local float g_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-thread_local int32_t g_counts[3] = {0, 0, 0};   // launches, lattices run again with more room, tuples over all lattices
-thread_local size_t g_workspace_limit = 0;
-
-template <typename T>
-struct Dev {
-  T *p = nullptr;
-  size_t n = 0;
-  ~Dev() { if (p) PoolFree(p); }
-  int Alloc(size_t count) {
-    if (p) PoolFree(p);
-    n = count ? count : 1;
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * n));
-    return p ? KH_OK : KH_ENOMEM;
-  }
-  int Grow(size_t count) { return p && count <= n ? KH_OK : Alloc(count); }
-  int Upload(const std::vector<T> &h, hipStream_t st) {
-    if (Alloc(h.size())) return KH_ENOMEM;
-    if (!h.empty() && hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return KH_EDEVICE;
-    return KH_OK;
-  }
-};
+// ms[5]: the host's finishing pass; counts: launches, lattices run again with more room, tuples over all lattices
+static thread_local CallStats<6, 3> g_stats;
 
 }  // namespace latalign
 }  // namespace kh
@@ -774,15 +752,12 @@ using namespace kh;
 using namespace kh::latalign;
 
 extern "C" int kh_compact_lattice_align_words_set_workspace_limit(size_t bytes) {
-  g_workspace_limit = bytes;
+  g_stats.workspace_limit = bytes;
   return KH_OK;
 }
 
 extern "C" int kh_compact_lattice_align_words_last_timings(float *ms6, int32_t *counts3) {
-  KH_CHECK_ARG(ms6);
-  for (int i = 0; i < 6; i++) ms6[i] = g_ms[i];
-  if (counts3) for (int i = 0; i < 3; i++) counts3[i] = g_counts[i];
-  return KH_OK;
+  return GetTimings(g_stats, ms6, counts3);
 }
 
 extern "C" int kh_compact_lattice_align_words(
@@ -806,43 +781,36 @@ extern "C" int kh_compact_lattice_align_words(
                out_arc_nextstate && out_arc_label && out_arc_graph && out_arc_acoustic && out_arc_string_len && out_strings);
   KH_CHECK_ARG(lat_state_offsets[0] == 0 && arc_offsets[0] == 0 && out_state_offsets[0] == 0 && out_arc_offsets[0] == 0 &&
                out_string_offsets[0] == 0 && silence_label >= 0 && partial_word_label >= 0);
-  const auto t0 = std::chrono::steady_clock::now();
+  CallTimer T;
   Prepared P;
   if ((rc = Prepare(n_lats, lat_state_offsets, lat_start, arc_offsets, arc_label, arc_nextstate, arc_graph, arc_acoustic,
                     arc_string_offsets, arc_strings, final_graph, final_acoustic, final_string_offsets, final_strings,
                     num_tids, tid_phone, tid_is_final, tid_is_self_loop, n_phone_types, phone_type, reorder, silence_label,
                     partial_word_label, max_states, &P)) != KH_OK)
     return rc;
-  const auto t1 = std::chrono::steady_clock::now();
+  T.HostDone();
   std::vector<OutLat> outs(n_lats);
   for (int l = 0; l < n_lats; l++) outs[l].status = P.job_of_lat[l] < 0 ? KH_ALIGN_EMPTY : KH_ALIGN_OK;
-  float ms_up = 0.f, ms_kernel = 0.f, ms_down = 0.f, ms = 0.f;
   double ms_finish = 0.0;
   int32_t n_launches = 0, n_again = 0;
   if (!P.jobs.empty()) {
     hipStream_t st = Stream();
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    for (int i = 0; i < 4; i++) KH_HIP(hipEventCreate(&ev[i]));
+    KH_HIP(T.Init());
     Dev<int32_t> d_arc_off, d_label, d_next, d_str_off, d_strings, d_tinfo, d_ptype, d_ws;
     Dev<float> d_g, d_a;
     Dev<AlignJob> d_jobs;
-    KH_HIP(hipEventRecord(ev[0], st));
+    KH_HIP(T.Mark(0, st));
     if (d_arc_off.Upload(P.arc_off, st) || d_label.Upload(P.arc_label, st) || d_next.Upload(P.arc_next, st) ||
         d_str_off.Upload(P.str_off, st) || d_strings.Upload(P.strings, st) || d_tinfo.Upload(P.tinfo, st) ||
         d_ptype.Upload(P.ptype, st) || d_g.Upload(P.arc_g, st) || d_a.Upload(P.arc_a, st)) {
       SetError("kh_compact_lattice_align_words: out of device memory");
       return KH_ENOMEM;
     }
-    KH_HIP(hipEventRecord(ev[1], st));
+    KH_HIP(T.Mark(1, st));
     KH_HIP(hipStreamSynchronize(st));
-    KH_HIP(hipEventElapsedTime(&ms_up, ev[0], ev[1]));
-    size_t limit = g_workspace_limit;
-    if (limit == 0) {
-      size_t free_b = 0, total_b = 0;
-      if ((rc = kh_mem_info(&free_b, &total_b)) != KH_OK) return rc;
-      limit = (free_b + PoolCachedBytes()) / 2;
-    }
+    KH_HIP(T.Add(&T.up, 0, 1));
+    size_t limit = g_stats.workspace_limit;   // by default half of what is free: nothing else of this call is allocated later
+    if (limit == 0 && (rc = DefaultWorkspaceLimit(0, &limit)) != KH_OK) return rc;
     std::vector<int32_t> todo(P.jobs.size());
     std::iota(todo.begin(), todo.end(), 0);
     std::vector<int32_t> h_ws;
@@ -880,12 +848,12 @@ extern "C" int kh_compact_lattice_align_words(
         }
         if (h_ws.size() < words) h_ws.resize(words);
         AlignCtx X{d_arc_off.p, d_label.p, d_next.p, d_g.p, d_a.p, d_str_off.p, d_strings.p, d_tinfo.p, d_ptype.p, P.reorder, d_ws.p};
-        KH_HIP(hipEventRecord(ev[0], st));
-        KH_HIP(hipMemcpyAsync(d_jobs.p, batch.data(), sizeof(AlignJob) * batch.size(), hipMemcpyHostToDevice, st));
-        KH_HIP(hipEventRecord(ev[1], st));
+        KH_HIP(T.Mark(0, st));
+        KH_HIP(Up(d_jobs, batch.data(), batch.size(), st));
+        KH_HIP(T.Mark(1, st));
         hipLaunchKernelGGL(AlignKernel, dim3(static_cast<unsigned>(batch.size())), dim3(kLanes), 0, st, d_jobs.p, X);
         KH_LAUNCH_CHECK();
-        KH_HIP(hipEventRecord(ev[2], st));
+        KH_HIP(T.Mark(2, st));
         // the headers first; then of every finished lattice its tuples, pairs and the used part of its arena
         KH_HIP(hipMemcpyAsync(h_ws.data(), d_ws.p, sizeof(int32_t) * hdr_words, hipMemcpyDeviceToHost, st));
         KH_HIP(hipStreamSynchronize(st));
@@ -899,14 +867,9 @@ extern "C" int kh_compact_lattice_align_words(
           }
           KH_HIP(hipMemcpyAsync(h_ws.data() + J.ws_off, d_ws.p + J.ws_off, sizeof(int32_t) * ResultWords(J, h[3]), hipMemcpyDeviceToHost, st));
         }
-        KH_HIP(hipEventRecord(ev[3], st));
+        KH_HIP(T.Mark(3, st));
         KH_HIP(hipStreamSynchronize(st));
-        KH_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ms_up += ms;
-        KH_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-        ms_kernel += ms;
-        KH_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-        ms_down += ms;
+        KH_HIP(T.AddAll());
         n_launches++;
         const auto f0 = std::chrono::steady_clock::now();
         for (size_t k = 0; k < batch.size(); k++) {
@@ -955,12 +918,12 @@ extern "C" int kh_compact_lattice_align_words(
       fits = false;
     }
   }
-  g_ms[0] = static_cast<float>(std::chrono::duration<double, std::milli>(t1 - t0).count());
-  g_ms[1] = ms_up; g_ms[2] = ms_kernel; g_ms[3] = ms_down;
-  g_ms[5] = static_cast<float>(ms_finish);
-  g_counts[0] = n_launches; g_counts[1] = n_again; g_counts[2] = static_cast<int32_t>(std::min<int64_t>(tuples, INT32_MAX));
+  g_stats.ms[5] = static_cast<float>(ms_finish);
+  g_stats.counts[0] = n_launches;
+  g_stats.counts[1] = n_again;
+  g_stats.counts[2] = static_cast<int32_t>(std::min<int64_t>(tuples, INT32_MAX));
   if (!fits) {
-    g_ms[4] = static_cast<float>(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    T.Finish(g_stats.ms);
     SetError("kh_compact_lattice_align_words: lattice %d: %d states, %d arcs, %lld transition-ids do not fit the room of %lld, %lld, "
              "%lld", first_short, n_states[first_short], n_arcs[first_short], static_cast<long long>(n_string_words[first_short]),
              static_cast<long long>(out_state_offsets[first_short + 1] - out_state_offsets[first_short]),
@@ -981,6 +944,6 @@ extern "C" int kh_compact_lattice_align_words(
     std::copy(O.arc_len.begin(), O.arc_len.end(), out_arc_string_len + a0);
     std::copy(O.strings.begin(), O.strings.end(), out_strings + out_string_offsets[l]);
   }
-  g_ms[4] = static_cast<float>(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  T.Finish(g_stats.ms);
   return KH_OK;
 }

@@ -16,13 +16,13 @@
 //     differ can round to the same my_cost + arc_cost, and then the relaxation kept the first while :1113 takes the cheaper.
 // The lanes never exchange data, so there are no barriers and no cross-lane operations.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
-#include <numeric>
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_latbatch.h"
+#include "kh_scorepoint.h"
 
 namespace kh {
 namespace {
@@ -40,30 +40,6 @@ struct BpLat {
   int32_t pad;
 };
 
-struct Point {
-  double s00, s01, s10, s11;
-  float pen;
-};
-
-// ScaleTupleWeight fstext/lattice-weight.h:233-241: Zero stays Zero (:237-238); products and sums in double, the
-// LatticeWeightTpl<float> constructor narrows.
-__device__ __forceinline__ void ScaleWeight(float g, float a, const Point &pt, float *g2, float *a2) {
-  if (g == INFINITY) {
-    *g2 = INFINITY;
-    *a2 = INFINITY;
-  } else {
-    *g2 = static_cast<float>(pt.s00 * static_cast<double>(g) + pt.s01 * static_cast<double>(a));
-    *a2 = static_cast<float>(pt.s10 * static_cast<double>(g) + pt.s11 * static_cast<double>(a));
-  }
-}
-// ... followed by AddWordInsPenToCompactLattice lat/lattice-functions.cc:1140-1143 (float sum, arcs with a word only)
-__device__ __forceinline__ void ArcWeight(float g, float a, int32_t label, const Point &pt, float *g2, float *a2) {
-  ScaleWeight(g, a, pt, g2, a2);
-  if (label != 0) *g2 = *g2 + pt.pen;
-}
-// ConvertToCost fstext/lattice-weight.h:799-801
-__device__ __forceinline__ double Cost(float g2, float a2) { return static_cast<double>(g2) + static_cast<double>(a2); }
-
 __global__ __launch_bounds__(kLanes) void BestPathKernel(
     const BpLat *__restrict__ lats, const int64_t *__restrict__ in_off, const int32_t *__restrict__ in_src,
     const int32_t *__restrict__ in_arc, const int32_t *__restrict__ in_label, const float *__restrict__ in_g,
@@ -74,12 +50,7 @@ __global__ __launch_bounds__(kLanes) void BestPathKernel(
   const BpLat L = lats[blockIdx.x];
   const int p = blockIdx.y * kLanes + threadIdx.x;
   if (p >= n_points) return;
-  Point pt;
-  pt.s00 = scales[4 * p];
-  pt.s01 = scales[4 * p + 1];
-  pt.s10 = scales[4 * p + 2];
-  pt.s11 = scales[4 * p + 3];
-  pt.pen = penalties[p];
+  const Point pt = LoadPoint(scales, penalties, p);
   const int64_t P = n_points;
   double *c = cost + L.ws_row * P + p;
   int32_t *pr = pred + L.ws_row * P + p;
@@ -181,19 +152,7 @@ __global__ __launch_bounds__(kLanes) void BestPathKernel(
   out_a[o] = ta;
 }
 
-template <typename T>
-struct Dev {
-  T *p = nullptr;
-  ~Dev() { if (p) PoolFree(p); }
-  int Alloc(size_t n) {
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * (n ? n : 1)));
-    return p ? KH_OK : KH_ENOMEM;
-  }
-};
-
-thread_local float g_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-thread_local int32_t g_calls = 0;        // kernel launches of the last call
-thread_local size_t g_workspace_limit = 0;   // of the calling thread; 0: from kh_mem_info
+thread_local CallStats<5, 1> g_stats;   // counts: kernel launches of the last call
 
 }  // namespace
 }  // namespace kh
@@ -201,15 +160,12 @@ thread_local size_t g_workspace_limit = 0;   // of the calling thread; 0: from k
 using namespace kh;
 
 extern "C" int kh_compact_lattice_best_paths_set_workspace_limit(size_t bytes) {
-  g_workspace_limit = bytes;
+  g_stats.workspace_limit = bytes;
   return KH_OK;
 }
 
 extern "C" int kh_compact_lattice_best_paths_last_timings(float *ms5, int32_t *n_launches) {
-  KH_CHECK_ARG(ms5);
-  for (int i = 0; i < 5; i++) ms5[i] = g_ms[i];
-  if (n_launches) *n_launches = g_calls;
-  return KH_OK;
+  return GetTimings(g_stats, ms5, n_launches);
 }
 
 extern "C" int kh_compact_lattice_best_paths(int n_lats, const int32_t *lat_state_offsets, const int64_t *arc_offsets,
@@ -225,116 +181,92 @@ extern "C" int kh_compact_lattice_best_paths(int n_lats, const int32_t *lat_stat
                path_final_state && tot_graph && tot_acoustic);
   KH_CHECK_ARG(lat_state_offsets[0] == 0 && arc_offsets[0] == 0);
   for (int l = 0; l < n_lats; l++) KH_CHECK_ARG(lat_state_offsets[l + 1] - lat_state_offsets[l] > 0);
-  const auto t_host0 = std::chrono::steady_clock::now();
+  CallTimer T;
   const int64_t S = lat_state_offsets[n_lats], A = arc_offsets[S];
   KH_CHECK_ARG(A >= 0 && A < (1ll << 31));   // (positions in the incoming arrays are kept as int32 in the path rows)
   const int64_t P = n_points;
   for (int64_t i = 0; i < static_cast<int64_t>(n_lats) * P; i++) KH_CHECK_ARG(path_offsets[i + 1] >= path_offsets[i]);
 
-  // validation (top-sorted: every arc goes to a higher-numbered state of its own lattice; :1046, :1056) and the incoming
-  // lists: a counting sort by destination, which keeps the arcs of one destination in (source state, arc position) order
-  std::vector<int64_t> in_off(S + 1, 0);
+  // validation (:1046, :1056), the incoming lists, and per lattice the arcs on its longest path
   std::vector<BpLat> lats(n_lats);
-  for (int l = 0; l < n_lats; l++) {
-    const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
-    for (int32_t s = 0; s < ns; s++) {
-      KH_CHECK_ARG(arc_offsets[s0 + s + 1] >= arc_offsets[s0 + s]);
-      for (int64_t j = arc_offsets[s0 + s]; j < arc_offsets[s0 + s + 1]; j++) {
-        const int32_t nx = arc_nextstate[j];
-        if (nx <= s || nx >= ns) {
-          SetError("kh_compact_lattice_best_paths: lattice %d: arc %lld (state %d -> %d of %d): input lattice must be "
-                   "topologically sorted", l, static_cast<long long>(j - arc_offsets[s0]), s, nx, ns);
-          return KH_EINVAL;
-        }
-        in_off[s0 + nx + 1]++;
-      }
-    }
-  }
-  for (int64_t s = 0; s < S; s++) in_off[s + 1] += in_off[s];
-  std::vector<int32_t> in_src(A), in_arc(A), in_label(A);
+  std::vector<int32_t> depth, in_label(A);
   std::vector<float> in_g(A), in_a(A);
-  {
-    std::vector<int64_t> fill(in_off.begin(), in_off.end() - 1);
-    std::vector<int32_t> depth;
-    for (int l = 0; l < n_lats; l++) {
-      const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
-      const int64_t a0 = arc_offsets[s0];
-      depth.assign(ns, 0);
-      int32_t max_depth = 0;
-      for (int32_t s = 0; s < ns; s++) {
-        max_depth = std::max(max_depth, depth[s]);
-        for (int64_t j = arc_offsets[s0 + s]; j < arc_offsets[s0 + s + 1]; j++) {
-          const int32_t nx = arc_nextstate[j];
-          const int64_t k = fill[s0 + nx]++;
-          in_src[k] = s;
-          in_arc[k] = static_cast<int32_t>(j - a0);
-          in_label[k] = arc_label[j];
-          in_g[k] = arc_graph[j];
-          in_a[k] = arc_acoustic[j];
-          depth[nx] = std::max(depth[nx], depth[s] + 1);
-        }
-      }
-      BpLat &L = lats[l];
-      L.state_base = s0;
-      L.arc_base = a0;
-      L.n_states = ns;
-      L.depth = std::max(max_depth, 1);
-      L.lat = l;
-      L.pad = 0;
-    }
+  int32_t max_depth = 0;
+  Incoming in;
+  std::string err;
+  if (!BuildIncoming(
+          "kh_compact_lattice_best_paths", n_lats, lat_state_offsets, nullptr, arc_offsets, arc_nextstate, &in, &err,
+          [&](int, int32_t, int32_t ns) {
+            depth.assign(ns, 0);
+            max_depth = 0;
+            return true;
+          },
+          [&](int, int32_t, int32_t s) {
+            max_depth = std::max(max_depth, depth[s]);
+            return true;
+          },
+          [&](int, int32_t s, int64_t, int32_t nx) {
+            depth[nx] = std::max(depth[nx], depth[s] + 1);
+            return true;
+          },
+          [&](int l, int32_t s0, int32_t ns) {
+            BpLat &L = lats[l];
+            L.state_base = s0;
+            L.arc_base = arc_offsets[s0];
+            L.n_states = ns;
+            L.depth = std::max(max_depth, 1);
+            L.lat = l;
+            L.pad = 0;
+            return true;
+          },
+          [&](int, int64_t k, int64_t j) {
+            in_label[k] = arc_label[j];
+            in_g[k] = arc_graph[j];
+            in_a[k] = arc_acoustic[j];
+          })) {
+    SetError("%s", err.c_str());
+    return KH_EINVAL;
   }
   // the lattices in flight: longest first, as many as the workspace limit admits per launch (at least one)
-  std::vector<int32_t> order(n_lats);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return lats[x].n_states > lats[y].n_states; });
-  size_t limit = g_workspace_limit;
-  if (limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if ((rc = kh_mem_info(&free_b, &total_b)) != KH_OK) return rc;
-    const size_t fixed = static_cast<size_t>(A) * 20 + static_cast<size_t>(S) * 16;
-    const size_t avail = free_b + PoolCachedBytes();
-    limit = avail > 2 * fixed ? (avail - fixed) / 2 : avail / 4;
+  size_t limit = g_stats.workspace_limit;
+  if (limit == 0 && (rc = DefaultWorkspaceLimit(static_cast<size_t>(A) * 20 + static_cast<size_t>(S) * 16, &limit)) != KH_OK)
+    return rc;
+  std::vector<size_t> ws_bytes(n_lats), n_states(n_lats);
+  for (int l = 0; l < n_lats; l++) {
+    ws_bytes[l] = (static_cast<size_t>(lats[l].n_states) * 12 + static_cast<size_t>(lats[l].depth) * 4) * static_cast<size_t>(P);
+    n_states[l] = lats[l].n_states;
   }
-  auto ws_bytes = [&](const BpLat &L) {
-    return (static_cast<size_t>(L.n_states) * 12 + static_cast<size_t>(L.depth) * 4) * static_cast<size_t>(P);
-  };
-  struct Chunk { int32_t begin, end; int64_t ws_rows, path_rows; };
-  std::vector<Chunk> chunks;
+  const ChunkPlan plan = PlanChunks(ws_bytes, limit, 65535, &n_states);
+  struct Rows { int64_t ws, path; };
+  std::vector<Rows> rows;
   std::vector<BpLat> sorted(n_lats);
   int64_t max_ws_rows = 0, max_path_rows = 0;
-  for (int32_t i = 0; i < n_lats;) {
-    Chunk c{i, i, 0, 0};
-    size_t bytes = 0;
-    while (c.end < n_lats && c.end - c.begin < 65535) {
-      BpLat L = lats[order[c.end]];
-      const size_t b = ws_bytes(L);
-      if (c.end > c.begin && bytes + b > limit) break;
-      bytes += b;
-      L.ws_row = c.ws_rows;
-      L.path_row = c.path_rows;
-      c.ws_rows += L.n_states;
-      c.path_rows += L.depth;
-      sorted[c.end++] = L;
+  size_t max_chunk_lats = 0;
+  for (const ChunkRange &c : plan.ranges) {
+    Rows r{0, 0};
+    for (size_t i = c.begin; i < c.end; i++) {
+      BpLat L = lats[plan.order[i]];
+      L.ws_row = r.ws;
+      L.path_row = r.path;
+      r.ws += L.n_states;
+      r.path += L.depth;
+      sorted[i] = L;
     }
-    max_ws_rows = std::max(max_ws_rows, c.ws_rows);
-    max_path_rows = std::max(max_path_rows, c.path_rows);
-    chunks.push_back(c);
-    i = c.end;
+    max_ws_rows = std::max(max_ws_rows, r.ws);
+    max_path_rows = std::max(max_path_rows, r.path);
+    max_chunk_lats = std::max(max_chunk_lats, c.end - c.begin);
+    rows.push_back(r);
   }
-  const auto t_host1 = std::chrono::steady_clock::now();
+  T.HostDone();
 
   hipStream_t st = Stream();
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  for (int i = 0; i < 4; i++) KH_HIP(hipEventCreate(&ev[i]));
+  KH_HIP(T.Init());
   Dev<BpLat> d_lats;
   Dev<int64_t> d_in_off;
   Dev<int32_t> d_in_src, d_in_arc, d_in_label, d_pred, d_path, d_len, d_final, d_err;
   Dev<float> d_in_g, d_in_a, d_fin_g, d_fin_a, d_pen, d_tg, d_ta;
   Dev<double> d_scales, d_cost;
-  int32_t max_chunk_lats = 0;
-  for (const Chunk &c : chunks) max_chunk_lats = std::max(max_chunk_lats, c.end - c.begin);
-  const size_t LP = static_cast<size_t>(max_chunk_lats) * P;   // per-path results of one launch, in launch order
+  const size_t LP = max_chunk_lats * P;   // per-path results of one launch, in launch order
   if (d_lats.Alloc(n_lats) || d_in_off.Alloc(S + 1) || d_in_src.Alloc(A) || d_in_arc.Alloc(A) || d_in_label.Alloc(A) ||
       d_in_g.Alloc(A) || d_in_a.Alloc(A) || d_fin_g.Alloc(S) || d_fin_a.Alloc(S) || d_scales.Alloc(4 * P) || d_pen.Alloc(P) ||
       d_len.Alloc(LP) || d_final.Alloc(LP) || d_tg.Alloc(LP) || d_ta.Alloc(LP) || d_err.Alloc(1) ||
@@ -344,52 +276,45 @@ extern "C" int kh_compact_lattice_best_paths(int n_lats, const int32_t *lat_stat
              static_cast<long long>(max_ws_rows), n_points);
     return KH_ENOMEM;
   }
-#define UP(dev, host, count, type) KH_HIP(hipMemcpyAsync(dev.p, host, sizeof(type) * (count), hipMemcpyHostToDevice, st))
-  KH_HIP(hipEventRecord(ev[0], st));
-  UP(d_lats, sorted.data(), n_lats, BpLat);
-  UP(d_in_off, in_off.data(), S + 1, int64_t);
-  if (A > 0) {
-    UP(d_in_src, in_src.data(), A, int32_t);
-    UP(d_in_arc, in_arc.data(), A, int32_t);
-    UP(d_in_label, in_label.data(), A, int32_t);
-    UP(d_in_g, in_g.data(), A, float);
-    UP(d_in_a, in_a.data(), A, float);
-  }
-  UP(d_fin_g, final_graph, S, float);
-  UP(d_fin_a, final_acoustic, S, float);
-  UP(d_scales, scales, 4 * P, double);
-  UP(d_pen, penalties, P, float);
-#undef UP
+  KH_HIP(T.Mark(0, st));
+  KH_HIP(Up(d_lats, sorted.data(), n_lats, st));
+  KH_HIP(Up(d_in_off, in.in_off.data(), S + 1, st));
+  KH_HIP(Up(d_in_src, in.in_src.data(), A, st));
+  KH_HIP(Up(d_in_arc, in.in_arc.data(), A, st));
+  KH_HIP(Up(d_in_label, in_label.data(), A, st));
+  KH_HIP(Up(d_in_g, in_g.data(), A, st));
+  KH_HIP(Up(d_in_a, in_a.data(), A, st));
+  KH_HIP(Up(d_fin_g, final_graph, S, st));
+  KH_HIP(Up(d_fin_a, final_acoustic, S, st));
+  KH_HIP(Up(d_scales, scales, 4 * P, st));
+  KH_HIP(Up(d_pen, penalties, P, st));
   KH_HIP(hipMemsetAsync(d_err.p, 0, sizeof(int32_t), st));
-  KH_HIP(hipEventRecord(ev[1], st));
+  KH_HIP(T.Mark(1, st));
   KH_HIP(hipStreamSynchronize(st));
-  float ms_up = 0.f, ms_kernel = 0.f, ms_down = 0.f;
-  KH_HIP(hipEventElapsedTime(&ms_up, ev[0], ev[1]));
+  KH_HIP(T.Add(&T.up, 0, 1));
 
   std::vector<int32_t> h_path(static_cast<size_t>(max_path_rows) * P), h_len(LP), h_final(LP);
   std::vector<float> h_tg(LP), h_ta(LP);
   const int groups = static_cast<int>((P + kLanes - 1) / kLanes);
-  for (const Chunk &c : chunks) {
-    KH_HIP(hipEventRecord(ev[1], st));
+  for (size_t ci = 0; ci < plan.ranges.size(); ci++) {
+    const ChunkRange &c = plan.ranges[ci];
+    KH_HIP(T.Mark(1, st));
     hipLaunchKernelGGL(BestPathKernel, dim3(c.end - c.begin, groups), dim3(kLanes), 0, st, d_lats.p + c.begin, d_in_off.p,
                        d_in_src.p, d_in_arc.p, d_in_label.p, d_in_g.p, d_in_a.p, d_fin_g.p, d_fin_a.p, d_scales.p, d_pen.p,
                        n_points, d_cost.p, d_pred.p, d_path.p, d_len.p, d_final.p, d_tg.p, d_ta.p, d_err.p);
     KH_LAUNCH_CHECK();
-    KH_HIP(hipEventRecord(ev[2], st));
-    KH_HIP(hipMemcpyAsync(h_path.data(), d_path.p, sizeof(int32_t) * static_cast<size_t>(c.path_rows) * P, hipMemcpyDeviceToHost, st));
-    const size_t CP = static_cast<size_t>(c.end - c.begin) * P;
+    KH_HIP(T.Mark(2, st));
+    KH_HIP(hipMemcpyAsync(h_path.data(), d_path.p, sizeof(int32_t) * static_cast<size_t>(rows[ci].path) * P, hipMemcpyDeviceToHost, st));
+    const size_t CP = (c.end - c.begin) * P;
     KH_HIP(hipMemcpyAsync(h_len.data(), d_len.p, sizeof(int32_t) * CP, hipMemcpyDeviceToHost, st));
     KH_HIP(hipMemcpyAsync(h_final.data(), d_final.p, sizeof(int32_t) * CP, hipMemcpyDeviceToHost, st));
     KH_HIP(hipMemcpyAsync(h_tg.data(), d_tg.p, sizeof(float) * CP, hipMemcpyDeviceToHost, st));
     KH_HIP(hipMemcpyAsync(h_ta.data(), d_ta.p, sizeof(float) * CP, hipMemcpyDeviceToHost, st));
-    KH_HIP(hipEventRecord(ev[3], st));
+    KH_HIP(T.Mark(3, st));
     KH_HIP(hipStreamSynchronize(st));
-    float a = 0.f, b = 0.f;
-    KH_HIP(hipEventElapsedTime(&a, ev[1], ev[2]));
-    KH_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
-    ms_kernel += a;
-    ms_down += b;
-    for (int32_t i = c.begin; i < c.end; i++) {
+    KH_HIP(T.Add(&T.kernel, 1, 2));
+    KH_HIP(T.Add(&T.down, 2, 3));
+    for (size_t i = c.begin; i < c.end; i++) {
       const BpLat &L = sorted[i];
       for (int64_t p = 0; p < P; p++) {
         const int64_t o = static_cast<int64_t>(L.lat) * P + p, r = static_cast<int64_t>(i - c.begin) * P + p;
@@ -410,23 +335,17 @@ extern "C" int kh_compact_lattice_best_paths(int n_lats, const int32_t *lat_stat
       }
     }
   }
-  KH_HIP(hipEventRecord(ev[2], st));
+  KH_HIP(T.Mark(2, st));
   int32_t h_err = 0;
   KH_HIP(hipMemcpyAsync(&h_err, d_err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  KH_HIP(hipEventRecord(ev[3], st));
+  KH_HIP(T.Mark(3, st));
   KH_HIP(hipStreamSynchronize(st));
-  float b = 0.f;
-  KH_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
-  ms_down += b;
+  KH_HIP(T.Add(&T.down, 2, 3));
   if (h_err != 0) {
     SetError("kh_compact_lattice_best_paths: a path left the rows of its lattice (internal error)");
     return KH_ESTATE;
   }
-  g_ms[0] = std::chrono::duration<float, std::milli>(t_host1 - t_host0).count();
-  g_ms[1] = ms_up;
-  g_ms[2] = ms_kernel;
-  g_ms[3] = ms_down;
-  g_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-  g_calls = static_cast<int32_t>(chunks.size());
+  T.Finish(g_stats.ms);
+  g_stats.counts[0] = static_cast<int32_t>(plan.ranges.size());
   return KH_OK;
 }

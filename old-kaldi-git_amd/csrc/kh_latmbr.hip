@@ -41,6 +41,8 @@
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_latbatch.h"
+#include "kh_scorepoint.h"
 
 namespace kh {
 namespace {
@@ -58,13 +60,6 @@ struct MbrJob {
   int32_t V;
   int32_t pad;
 };
-
-// rows are written by some lanes and read by others of the same wave later in program order
-__device__ __forceinline__ void WaveFence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // :113-123 / :168-181 for one arc and the 64 positions from c0: returns alpha_dash_arc(q) and b_arc[q]; *carry is
 // alpha_dash_arc(c0 - 1) on entry and alpha_dash_arc(c0 + 63) on return.
@@ -231,20 +226,6 @@ __global__ __launch_bounds__(kLanes) void MbrAccStatsKernel(
   }
 }
 
-template <typename T>
-struct Dev {
-  T *p = nullptr;
-  size_t n = 0;
-  ~Dev() { if (p) PoolFree(p); }
-  int Alloc(size_t count) {
-    if (p) PoolFree(p);
-    n = count ? count : 1;
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * n));
-    return p ? KH_OK : KH_ENOMEM;
-  }
-  int Grow(size_t count) { return p && count <= n ? KH_OK : Alloc(count); }
-};
-
 // base/kaldi-math.h:178-195
 inline double LogAddDouble(double x, double y) {
   static const double kMinLogDiffDouble = std::log(DBL_EPSILON);   // base/kaldi-math.h:45
@@ -282,9 +263,7 @@ struct GammaCompare {
   }
 };
 
-thread_local float g_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-thread_local int32_t g_counts[3] = {0, 0, 0};   // launches, rounds of the host loop, AccStats() calls over all pairs
-thread_local size_t g_workspace_limit = 0;      // of the calling thread; 0: from kh_mem_info
+thread_local CallStats<6, 3> g_stats;   // ms[5]: the host loop; counts: launches, rounds of the host loop, AccStats() calls over all pairs
 
 }  // namespace
 }  // namespace kh
@@ -292,15 +271,12 @@ thread_local size_t g_workspace_limit = 0;      // of the calling thread; 0: fro
 using namespace kh;
 
 extern "C" int kh_compact_lattice_mbr_set_workspace_limit(size_t bytes) {
-  g_workspace_limit = bytes;
+  g_stats.workspace_limit = bytes;
   return KH_OK;
 }
 
 extern "C" int kh_compact_lattice_mbr_last_timings(float *ms6, int32_t *counts3) {
-  KH_CHECK_ARG(ms6);
-  for (int i = 0; i < 6; i++) ms6[i] = g_ms[i];
-  if (counts3) for (int i = 0; i < 3; i++) counts3[i] = g_counts[i];
-  return KH_OK;
+  return GetTimings(g_stats, ms6, counts3);
 }
 
 extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start,
@@ -326,7 +302,7 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
   KH_CHECK_ARG(lat_state_offsets[0] == 0 && arc_offsets[0] == 0 && hyp_offsets[0] == 0 && word_offsets[0] == 0 &&
                bin_offsets[0] == 0 && stat_offsets[0] == 0);
   for (int l = 0; l < n_lats; l++) KH_CHECK_ARG(lat_state_offsets[l + 1] - lat_state_offsets[l] > 0);
-  const auto t_host0 = std::chrono::steady_clock::now();
+  CallTimer T;
   const int64_t S = lat_state_offsets[n_lats], A = arc_offsets[S];
   KH_CHECK_ARG(A >= 0 && A < (1ll << 31));
   const int64_t P = n_points, LP = static_cast<int64_t>(n_lats) * P;
@@ -343,76 +319,64 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
   const float finf = std::numeric_limits<float>::infinity();
   const double dinf = std::numeric_limits<double>::infinity();
 
-  // validation and the incoming lists: a counting sort by destination, which keeps the arcs of one destination in
-  // (source state, arc position) order = pre_[n] (:297-313)
-  std::vector<int64_t> in_off(S + 1, 0);
-  for (int l = 0; l < n_lats; l++) {
-    const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
-    if (lat_start[l] != 0) {
-      SetError("kh_compact_lattice_mbr: lattice %d: start state %d: a top-sorted lattice starts at state 0", l, lat_start[l]);
-      return KH_EINVAL;
-    }
-    for (int32_t s = 0; s < ns; s++) {
-      KH_CHECK_ARG(arc_offsets[s0 + s + 1] >= arc_offsets[s0 + s]);
-      const float fg = final_graph[s0 + s], fa = final_acoustic[s0 + s];
-      const bool ok = s == ns - 1 ? (fg == 0.f && fa == 0.f && arc_offsets[s0 + s + 1] == arc_offsets[s0 + s]) : (fg == finf && fa == finf);
-      if (!ok) {
-        SetError("kh_compact_lattice_mbr: lattice %d: state %d of %d (final weight %g, %g, %lld arcs): the last state must be the "
-                 "single final state, with weight One and no arcs (compact_lattice_mbr_prepare)", l, s, ns, fg, fa,
-                 static_cast<long long>(arc_offsets[s0 + s + 1] - arc_offsets[s0 + s]));
-        return KH_EINVAL;
-      }
-      for (int64_t j = arc_offsets[s0 + s]; j < arc_offsets[s0 + s + 1]; j++) {
-        const int32_t nx = arc_nextstate[j];
-        if (nx <= s || nx >= ns) {
-          SetError("kh_compact_lattice_mbr: lattice %d: arc %lld (state %d -> %d of %d): input lattice must be "
-                   "topologically sorted", l, static_cast<long long>(j - arc_offsets[s0]), s, nx, ns);
-          return KH_EINVAL;
-        }
-        const float g = arc_graph[j], a = arc_acoustic[j];
-        if (std::isnan(g) || std::isnan(a) || g == -finf || a == -finf) {
-          SetError("kh_compact_lattice_mbr: lattice %d: arc %lld (state %d -> %d): weight %g, %g: NaN and -inf are not taken", l,
-                   static_cast<long long>(j - arc_offsets[s0]), s, nx, g, a);
-          return KH_EINVAL;
-        }
-        in_off[s0 + nx + 1]++;
-      }
-    }
+  // validation and the incoming lists, whose order is pre_[n]'s (:297-313); V: 0 and the lattice's distinct labels
+  std::vector<int32_t> in_label(A), in_v(A);
+  std::vector<int64_t> in_arc(A);                            // (arc numbers of the whole batch)
+  std::vector<std::vector<int32_t>> vocab(n_lats);
+  std::vector<int32_t> zero_at(n_lats);
+  Incoming in;
+  std::string err;
+  if (!BuildIncoming(
+          "kh_compact_lattice_mbr", n_lats, lat_state_offsets, nullptr, arc_offsets, arc_nextstate, &in, &err,
+          [&](int l, int32_t, int32_t) {
+            if (lat_start[l] == 0) return true;
+            return Refuse(&err, "kh_compact_lattice_mbr: lattice %d: start state %d: a top-sorted lattice starts at state 0", l,
+                          lat_start[l]);
+          },
+          [&](int l, int32_t s0, int32_t s) {
+            const int32_t ns = lat_state_offsets[l + 1] - s0;
+            const float fg = final_graph[s0 + s], fa = final_acoustic[s0 + s];
+            const int64_t n_arcs = arc_offsets[s0 + s + 1] - arc_offsets[s0 + s];
+            if (s == ns - 1 ? (fg == 0.f && fa == 0.f && n_arcs == 0) : (fg == finf && fa == finf)) return true;
+            return Refuse(&err, "kh_compact_lattice_mbr: lattice %d: state %d of %d (final weight %g, %g, %lld arcs): the last state "
+                          "must be the single final state, with weight One and no arcs (compact_lattice_mbr_prepare)", l, s, ns,
+                          fg, fa, static_cast<long long>(n_arcs));
+          },
+          [&](int l, int32_t s, int64_t j, int32_t nx) {
+            const float g = arc_graph[j], a = arc_acoustic[j];
+            if (!(std::isnan(g) || std::isnan(a) || g == -finf || a == -finf)) return true;
+            return Refuse(&err, "kh_compact_lattice_mbr: lattice %d: arc %lld (state %d -> %d): weight %g, %g: NaN and -inf are not "
+                          "taken", l, static_cast<long long>(j - arc_offsets[lat_state_offsets[l]]), s, nx, g, a);
+          },
+          [&](int l, int32_t s0, int32_t ns) {
+            std::vector<int32_t> &v = vocab[l];
+            v.assign(arc_label + arc_offsets[s0], arc_label + arc_offsets[s0 + ns]);
+            v.push_back(0);
+            std::sort(v.begin(), v.end());
+            v.erase(std::unique(v.begin(), v.end()), v.end());
+            zero_at[l] = static_cast<int32_t>(std::lower_bound(v.begin(), v.end(), 0) - v.begin());
+            return true;
+          },
+          [&](int l, int64_t k, int64_t j) {
+            const std::vector<int32_t> &ascending = vocab[l];
+            const int32_t at = static_cast<int32_t>(std::lower_bound(ascending.begin(), ascending.end(), arc_label[j]) - ascending.begin());
+            const int32_t z = zero_at[l];
+            in_arc[k] = j;
+            in_label[k] = arc_label[j];
+            in_v[k] = at == z ? 0 : (at < z ? at + 1 : at);
+          })) {
+    SetError("%s", err.c_str());
+    return KH_EINVAL;
   }
-  for (int64_t s = 0; s < S; s++) in_off[s + 1] += in_off[s];
-  std::vector<int32_t> in_src(A), in_label(A), in_v(A);
-  std::vector<int64_t> in_arc(A);
-  std::vector<std::vector<int32_t>> vocab(n_lats);           // V: 0 and the lattice's distinct labels, ascending
-  {
-    std::vector<int64_t> fill(in_off.begin(), in_off.end() - 1);
-    for (int l = 0; l < n_lats; l++) {
-      const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
-      std::vector<int32_t> &v = vocab[l];
-      v.assign(arc_label + arc_offsets[s0], arc_label + arc_offsets[s0 + ns]);
-      v.push_back(0);
-      std::sort(v.begin(), v.end());
-      v.erase(std::unique(v.begin(), v.end()), v.end());
-      const std::vector<int32_t> ascending(v);
-      const int32_t zero_at = static_cast<int32_t>(std::lower_bound(ascending.begin(), ascending.end(), 0) - ascending.begin());
-      std::rotate(v.begin(), v.begin() + zero_at, v.begin() + zero_at + 1);   // 0 comes first: column 0 is epsilon's
-      for (int32_t s = 0; s < ns; s++) {
-        for (int64_t j = arc_offsets[s0 + s]; j < arc_offsets[s0 + s + 1]; j++) {
-          const int64_t k = fill[s0 + arc_nextstate[j]]++;
-          const int32_t at = static_cast<int32_t>(std::lower_bound(ascending.begin(), ascending.end(), arc_label[j]) - ascending.begin());
-          in_src[k] = s;
-          in_arc[k] = j;
-          in_label[k] = arc_label[j];
-          in_v[k] = at == zero_at ? 0 : (at < zero_at ? at + 1 : at);
-        }
-      }
-    }
-  }
+  for (int l = 0; l < n_lats; l++)                           // 0 comes first: column 0 is epsilon's
+    std::rotate(vocab[l].begin(), vocab[l].begin() + zero_at[l], vocab[l].begin() + zero_at[l] + 1);
+  const std::vector<int64_t> &in_off = in.in_off;
+  const std::vector<int32_t> &in_src = in.in_src;
   // per (lattice, point): loglike (:306-307), alpha (:102-107), w_a (:125)
   std::vector<double> w(static_cast<size_t>(A) * P), alpha;
   std::vector<float> ll(A);
   for (int64_t p = 0; p < P; p++) {
-    const double s00 = scales[4 * p], s01 = scales[4 * p + 1], s10 = scales[4 * p + 2], s11 = scales[4 * p + 3];
-    const float pen = penalties[p];
+    const Point pt = LoadPoint(scales, penalties, static_cast<int>(p));
     for (int l = 0; l < n_lats; l++) {
       const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
       alpha.assign(ns, 0.0);
@@ -420,15 +384,8 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
         double alpha_n = -dinf;                              // :102
         for (int64_t k = in_off[s0 + s]; k < in_off[s0 + s + 1]; k++) {
           const int64_t j = in_arc[k];
-          float g2, a2;                                      // ScaleTupleWeight fstext/lattice-weight.h:233-241
-          if (arc_graph[j] == finf) {
-            g2 = finf;
-            a2 = finf;
-          } else {
-            g2 = static_cast<float>(s00 * static_cast<double>(arc_graph[j]) + s01 * static_cast<double>(arc_acoustic[j]));
-            a2 = static_cast<float>(s10 * static_cast<double>(arc_graph[j]) + s11 * static_cast<double>(arc_acoustic[j]));
-          }
-          if (in_label[k] != 0) g2 = g2 + pen;               // lat/lattice-functions.cc:1140-1143
+          float g2, a2;
+          ArcWeight(arc_graph[j], arc_acoustic[j], in_label[k], pt, &g2, &a2);
           const float loglike = -(g2 + a2);                  // :306-307
           if (std::isnan(loglike) || loglike == finf) {
             SetError("kh_compact_lattice_mbr: lattice %d, point %d: arc %lld: the scaled weight %g, %g: NaN and -inf are not taken",
@@ -451,20 +408,14 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
   }
   std::vector<Pair> pairs(LP);
   for (int64_t o = 0; o < LP; o++) pairs[o].R.assign(hyp_words + hyp_offsets[o], hyp_words + hyp_offsets[o + 1]);   // :342 / :358
-  size_t limit = g_workspace_limit;
-  if (limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if ((rc = kh_mem_info(&free_b, &total_b)) != KH_OK) return rc;
-    const size_t fixed = static_cast<size_t>(A) * (12 + 8 * P) + static_cast<size_t>(S) * 12 + 64 * static_cast<size_t>(LP);
-    const size_t avail = free_b + PoolCachedBytes();
-    limit = avail > 2 * fixed ? (avail - fixed) / 2 : avail / 4;
-  }
-  const auto t_host1 = std::chrono::steady_clock::now();
+  size_t limit = g_stats.workspace_limit;
+  if (limit == 0 && (rc = DefaultWorkspaceLimit(static_cast<size_t>(A) * (12 + 8 * P) + static_cast<size_t>(S) * 12 +
+                                                    64 * static_cast<size_t>(LP), &limit)) != KH_OK)
+    return rc;
+  T.HostDone();
 
   hipStream_t st = Stream();
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  for (int i = 0; i < 4; i++) KH_HIP(hipEventCreate(&ev[i]));
+  KH_HIP(T.Init());
   Dev<int64_t> d_in_off;
   Dev<int32_t> d_in_src, d_in_label, d_in_v, d_times, d_r;
   Dev<double> d_w, d_ws, d_out;
@@ -474,20 +425,16 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
     SetError("kh_compact_lattice_mbr: out of device memory");
     return KH_ENOMEM;
   }
-#define UP(dev, host, count, type) KH_HIP(hipMemcpyAsync(dev.p, host, sizeof(type) * (count), hipMemcpyHostToDevice, st))
-  float ms_up = 0.f, ms_kernel = 0.f, ms_down = 0.f, ms = 0.f;
-  KH_HIP(hipEventRecord(ev[0], st));
-  UP(d_in_off, in_off.data(), S + 1, int64_t);
-  UP(d_times, state_times, S, int32_t);
-  if (A > 0) {
-    UP(d_in_src, in_src.data(), A, int32_t);
-    UP(d_in_label, in_label.data(), A, int32_t);
-    UP(d_in_v, in_v.data(), A, int32_t);
-    UP(d_w, w.data(), static_cast<size_t>(A) * P, double);
-  }
-  KH_HIP(hipEventRecord(ev[1], st));
+  KH_HIP(T.Mark(0, st));
+  KH_HIP(Up(d_in_off, in_off.data(), S + 1, st));
+  KH_HIP(Up(d_times, state_times, S, st));
+  KH_HIP(Up(d_in_src, in_src.data(), A, st));
+  KH_HIP(Up(d_in_label, in_label.data(), A, st));
+  KH_HIP(Up(d_in_v, in_v.data(), A, st));
+  KH_HIP(Up(d_w, w.data(), static_cast<size_t>(A) * P, st));
+  KH_HIP(T.Mark(1, st));
   KH_HIP(hipStreamSynchronize(st));
-  KH_HIP(hipEventElapsedTime(&ms_up, ev[0], ev[1]));
+  KH_HIP(T.Add(&T.up, 0, 1));
 
   // MbrDecode :27-69 for every pair; the staging vectors are reused between the rounds
   std::vector<MbrJob> jobs;
@@ -532,34 +479,29 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
     // the pairs in flight: largest first, as many per launch as the workspace limit admits (at least one)
     auto ws_cells = [](const MbrJob &J) { return 2 * static_cast<size_t>(J.n_states) * (J.Q + 1) + static_cast<size_t>(J.Q + 2) / 2; };
     auto out_cells = [](const MbrJob &J) { return (static_cast<size_t>(J.V) + 2) * (J.Q + 1) + 1; };
-    std::vector<int32_t> order(jobs.size());
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-      return ws_cells(jobs[x]) + out_cells(jobs[x]) > ws_cells(jobs[y]) + out_cells(jobs[y]);
-    });
+    std::vector<size_t> job_bytes(jobs.size());
+    for (size_t i = 0; i < jobs.size(); i++) job_bytes[i] = (ws_cells(jobs[i]) + out_cells(jobs[i])) * sizeof(double);
+    const ChunkPlan plan = PlanChunks(job_bytes, limit);
     std::vector<MbrJob> sorted(jobs.size());
     std::vector<int64_t> sorted_pair(jobs.size());
     struct Chunk { size_t begin, end, ws, out, out_base; };
     std::vector<Chunk> chunks;
     size_t max_ws = 0, max_out = 0, out_total = 0;
-    for (size_t i = 0; i < jobs.size();) {
-      Chunk c{i, i, 0, 0, out_total};
-      while (c.end < jobs.size() && c.end - c.begin < 65535) {
-        MbrJob J = jobs[order[c.end]];
-        const size_t a = ws_cells(J), b = out_cells(J);
-        if (c.end > c.begin && (c.ws + c.out + a + b) * sizeof(double) > limit) break;
+    for (const ChunkRange &r : plan.ranges) {
+      Chunk c{r.begin, r.end, 0, 0, out_total};
+      for (size_t i = r.begin; i < r.end; i++) {
+        MbrJob J = jobs[plan.order[i]];
         J.ws_off = static_cast<int64_t>(c.ws);
         J.out_off = static_cast<int64_t>(c.out);
-        c.ws += a;
-        c.out += b;
-        sorted_pair[c.end] = job_pair[order[c.end]];
-        sorted[c.end++] = J;
+        c.ws += ws_cells(J);
+        c.out += out_cells(J);
+        sorted_pair[i] = job_pair[plan.order[i]];
+        sorted[i] = J;
       }
       max_ws = std::max(max_ws, c.ws);
       max_out = std::max(max_out, c.out);
       out_total += c.out;
       chunks.push_back(c);
-      i = c.end;
     }
     if (d_ws.Grow(max_ws) || d_out.Grow(max_out) || d_r.Grow(rw.size())) {
       SetError("kh_compact_lattice_mbr: out of device memory (workspace of %lld + %lld doubles)", static_cast<long long>(max_ws),
@@ -567,28 +509,25 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
       return KH_ENOMEM;
     }
     if (h_out.size() < out_total) h_out.resize(out_total);
-    KH_HIP(hipEventRecord(ev[0], st));
-    UP(d_jobs, sorted.data(), sorted.size(), MbrJob);
-    UP(d_r, rw.data(), rw.size(), int32_t);
-    KH_HIP(hipEventRecord(ev[1], st));
+    KH_HIP(T.Mark(0, st));
+    KH_HIP(Up(d_jobs, sorted.data(), sorted.size(), st));
+    KH_HIP(Up(d_r, rw.data(), rw.size(), st));
+    KH_HIP(T.Mark(1, st));
     KH_HIP(hipStreamSynchronize(st));
-    KH_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ms_up += ms;
+    KH_HIP(T.Add(&T.up, 0, 1));
     for (const Chunk &c : chunks) {
-      KH_HIP(hipEventRecord(ev[1], st));
+      KH_HIP(T.Mark(1, st));
       KH_HIP(hipMemsetAsync(d_ws.p, 0, sizeof(double) * c.ws, st));
       KH_HIP(hipMemsetAsync(d_out.p, 0, sizeof(double) * c.out, st));
       hipLaunchKernelGGL(MbrAccStatsKernel, dim3(static_cast<unsigned>(c.end - c.begin)), dim3(kLanes), 0, st, d_jobs.p + c.begin,
                          d_in_off.p, d_in_src.p, d_in_label.p, d_in_v.p, d_w.p, d_times.p, d_r.p, d_ws.p, d_out.p);
       KH_LAUNCH_CHECK();
-      KH_HIP(hipEventRecord(ev[2], st));
+      KH_HIP(T.Mark(2, st));
       KH_HIP(hipMemcpyAsync(h_out.data() + c.out_base, d_out.p, sizeof(double) * c.out, hipMemcpyDeviceToHost, st));
-      KH_HIP(hipEventRecord(ev[3], st));
+      KH_HIP(T.Mark(3, st));
       KH_HIP(hipStreamSynchronize(st));
-      KH_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-      ms_kernel += ms;
-      KH_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-      ms_down += ms;
+      KH_HIP(T.Add(&T.kernel, 1, 2));
+      KH_HIP(T.Add(&T.down, 2, 3));
       n_launches++;
     }
     const auto t_loop0 = std::chrono::steady_clock::now();
@@ -661,7 +600,6 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
     }
     ms_loop += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_loop0).count();
   }
-#undef UP
   // the outputs, where they fit
   bool fits = true;
   int64_t bad = -1;
@@ -691,15 +629,11 @@ extern "C" int kh_compact_lattice_mbr(int n_lats, const int32_t *lat_state_offse
       std::copy(pr.stat_post.begin(), pr.stat_post.end(), stat_post + stat_offsets[o]);
     }
   }
-  g_ms[0] = std::chrono::duration<float, std::milli>(t_host1 - t_host0).count();
-  g_ms[1] = ms_up;
-  g_ms[2] = ms_kernel;
-  g_ms[3] = ms_down;
-  g_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-  g_ms[5] = ms_loop;
-  g_counts[0] = n_launches;
-  g_counts[1] = n_rounds;
-  g_counts[2] = n_acc;
+  T.Finish(g_stats.ms);
+  g_stats.ms[5] = ms_loop;
+  g_stats.counts[0] = n_launches;
+  g_stats.counts[1] = n_rounds;
+  g_stats.counts[2] = n_acc;
   if (!fits) {
     SetError("kh_compact_lattice_mbr: lattice %d, point %d: %d words, %d bins, %d statistics do not fit the room of %lld, %lld, "
              "%lld the offsets leave (n_words, n_bins and n_stats hold what every pair needs)", static_cast<int>(bad / P),

@@ -32,11 +32,10 @@
 // the same kernel: the lanes test 64 incoming arcs of the cell at once and one __ballot picks the first.  The frame sum is a
 // wave reduction at the head of it.
 #include <algorithm>
-#include <chrono>
-#include <numeric>
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_latbatch.h"
 
 namespace kh {
 namespace {
@@ -57,13 +56,6 @@ struct OrLat {
   int32_t lat;         // index in the caller's batch
   int32_t pad;
 };
-
-// rows are written by some lanes and read by others of the same wave later in program order
-__device__ __forceinline__ void WaveFence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ bool Bit(const uint64_t *m, int64_t i, int64_t W, int p) {
   return m == nullptr || ((m[i * W + (p >> 6)] >> (p & 63)) & 1) != 0;
@@ -216,19 +208,7 @@ __global__ __launch_bounds__(kLanes) void OracleKernel(
   }
 }
 
-template <typename T>
-struct Dev {
-  T *p = nullptr;
-  ~Dev() { if (p) PoolFree(p); }
-  int Alloc(size_t n) {
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * (n ? n : 1)));
-    return p ? KH_OK : KH_ENOMEM;
-  }
-};
-
-thread_local float g_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-thread_local int32_t g_calls = 0;            // OracleKernel launches of the last call
-thread_local size_t g_workspace_limit = 0;   // of the calling thread; 0: from kh_mem_info
+thread_local CallStats<5, 1> g_stats;   // counts: OracleKernel launches of the last call
 
 }  // namespace
 }  // namespace kh
@@ -236,15 +216,12 @@ thread_local size_t g_workspace_limit = 0;   // of the calling thread; 0: from k
 using namespace kh;
 
 extern "C" int kh_compact_lattice_oracle_set_workspace_limit(size_t bytes) {
-  g_workspace_limit = bytes;
+  g_stats.workspace_limit = bytes;
   return KH_OK;
 }
 
 extern "C" int kh_compact_lattice_oracle_last_timings(float *ms5, int32_t *n_launches) {
-  KH_CHECK_ARG(ms5);
-  for (int i = 0; i < 5; i++) ms5[i] = g_ms[i];
-  if (n_launches) *n_launches = g_calls;
-  return KH_OK;
+  return GetTimings(g_stats, ms5, n_launches);
 }
 
 extern "C" int kh_compact_lattice_oracle(int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start,
@@ -276,125 +253,84 @@ extern "C" int kh_compact_lattice_oracle(int n_lats, const int32_t *lat_state_of
   KH_CHECK_ARG(lat_state_offsets[0] == 0 && arc_offsets[0] == 0 && ref_offsets[0] == 0 && path_offsets[0] == 0);
   for (int l = 0; l < n_lats; l++) KH_CHECK_ARG(lat_state_offsets[l + 1] - lat_state_offsets[l] > 0);
   for (int i = 1; i < n_wildcards; i++) KH_CHECK_ARG(wildcards[i] > wildcards[i - 1]);
-  const auto t_host0 = std::chrono::steady_clock::now();
+  CallTimer T;
   const int64_t S = lat_state_offsets[n_lats], A = arc_offsets[S];
   KH_CHECK_ARG(A >= 0 && A < (1ll << 31));   // (arc positions within a lattice are kept as int32 in the incoming lists)
   const int64_t P = n_points, W = (P + kLanes - 1) / kLanes;
   // MapWildCards lattice-oracle.cc:58-75: a wildcard is epsilon, on the lattice (:88) and in the reference (:333)
   auto word = [&](int32_t w) { return std::binary_search(wildcards, wildcards + n_wildcards, w) ? 0 : w; };
 
-  // validation and the incoming lists: a counting sort by destination, which keeps the arcs of one destination in
-  // (source state, arc position) order, that is by ascending arc number
-  std::vector<int64_t> in_off(S + 1, 0);
+  // validation and the incoming lists (ascending arc number within a state's list)
   std::vector<OrLat> lats(n_lats);
-  std::vector<int32_t> refw;
-  for (int l = 0; l < n_lats; l++) {
-    const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
-    if (lat_start[l] < 0 || lat_start[l] >= ns) {
-      SetError("kh_compact_lattice_oracle: lattice %d: start state %d of %d states", l, lat_start[l], ns);
-      return KH_EINVAL;
-    }
-    if (ref_offsets[l + 1] < ref_offsets[l]) {
-      SetError("kh_compact_lattice_oracle: lattice %d: ref_offsets %lld, %lld: the offsets must ascend", l,
-               static_cast<long long>(ref_offsets[l]), static_cast<long long>(ref_offsets[l + 1]));
-      return KH_EINVAL;
-    }
-    if (ref_offsets[l + 1] - ref_offsets[l] >= kMaxRefWords) {
-      SetError("kh_compact_lattice_oracle: lattice %d: a reference of %lld words: at most %d are taken", l,
-               static_cast<long long>(ref_offsets[l + 1] - ref_offsets[l]), kMaxRefWords - 1);
-      return KH_EINVAL;
-    }
-    KH_CHECK_ARG(ref_offsets[l + 1] == ref_offsets[l] || ref_words);
-    for (int32_t s = 0; s < ns; s++) {
-      KH_CHECK_ARG(arc_offsets[s0 + s + 1] >= arc_offsets[s0 + s]);
-      for (int64_t j = arc_offsets[s0 + s]; j < arc_offsets[s0 + s + 1]; j++) {
-        const int32_t nx = arc_nextstate[j];
-        if (nx <= s || nx >= ns) {
-          SetError("kh_compact_lattice_oracle: lattice %d: arc %lld (state %d -> %d of %d): input lattice must be "
-                   "topologically sorted", l, static_cast<long long>(j - arc_offsets[s0]), s, nx, ns);
-          return KH_EINVAL;
-        }
-        in_off[s0 + nx + 1]++;
-      }
-    }
-    for (int64_t p = 0; p < P; p++) {
-      const int64_t o = static_cast<int64_t>(l) * P + p, room = path_offsets[o + 1] - path_offsets[o];
-      if (room < ns - 1) {
-        SetError("kh_compact_lattice_oracle: lattice %d, point %d: path_offsets leaves room for %lld arcs, a path may have %d",
-                 l, static_cast<int>(p), static_cast<long long>(room), ns - 1);
-        return KH_EINVAL;
-      }
-    }
-    OrLat &L = lats[l];
-    L.state_base = s0;
-    L.arc_base = arc_offsets[s0];
-    L.ws_off = 0;
-    L.ref_base = static_cast<int64_t>(refw.size());
-    L.n_states = ns;
-    L.n_arcs = static_cast<int32_t>(arc_offsets[s0 + ns] - arc_offsets[s0]);
-    L.start = lat_start[l];
-    L.lat = l;
-    L.pad = 0;
-    for (int64_t i = ref_offsets[l]; i < ref_offsets[l + 1]; i++)
-      if (word(ref_words[i]) != 0) refw.push_back(ref_words[i]);
-    L.R = static_cast<int32_t>(static_cast<int64_t>(refw.size()) - L.ref_base);
-  }
-  for (int64_t s = 0; s < S; s++) in_off[s + 1] += in_off[s];
-  std::vector<int32_t> in_src(A), in_arc(A), in_label(A);
-  {
-    std::vector<int64_t> fill(in_off.begin(), in_off.end() - 1);
-    for (int l = 0; l < n_lats; l++) {
-      const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
-      const int64_t a0 = arc_offsets[s0];
-      for (int32_t s = 0; s < ns; s++) {
-        for (int64_t j = arc_offsets[s0 + s]; j < arc_offsets[s0 + s + 1]; j++) {
-          const int64_t k = fill[s0 + arc_nextstate[j]]++;
-          in_src[k] = s;
-          in_arc[k] = static_cast<int32_t>(j - a0);
-          in_label[k] = word(arc_label[j]);
-        }
-      }
-    }
+  std::vector<int32_t> refw, in_label(A);
+  Incoming in;
+  std::string err;
+  if (!BuildIncoming(
+          "kh_compact_lattice_oracle", n_lats, lat_state_offsets, lat_start, arc_offsets, arc_nextstate, &in, &err,
+          [&](int l, int32_t, int32_t) {
+            if (ref_offsets[l + 1] < ref_offsets[l])
+              return Refuse(&err, "kh_compact_lattice_oracle: lattice %d: ref_offsets %lld, %lld: the offsets must ascend", l,
+                            static_cast<long long>(ref_offsets[l]), static_cast<long long>(ref_offsets[l + 1]));
+            if (ref_offsets[l + 1] - ref_offsets[l] >= kMaxRefWords)
+              return Refuse(&err, "kh_compact_lattice_oracle: lattice %d: a reference of %lld words: at most %d are taken", l,
+                            static_cast<long long>(ref_offsets[l + 1] - ref_offsets[l]), kMaxRefWords - 1);
+            KH_REFUSE_ARG(&err, ref_offsets[l + 1] == ref_offsets[l] || ref_words);
+            return true;
+          },
+          NoStateHook(), NoArcHook(),
+          [&](int l, int32_t s0, int32_t ns) {
+            for (int64_t p = 0; p < P; p++) {
+              const int64_t o = static_cast<int64_t>(l) * P + p, room = path_offsets[o + 1] - path_offsets[o];
+              if (room < ns - 1)
+                return Refuse(&err, "kh_compact_lattice_oracle: lattice %d, point %d: path_offsets leaves room for %lld arcs, a "
+                              "path may have %d", l, static_cast<int>(p), static_cast<long long>(room), ns - 1);
+            }
+            OrLat &L = lats[l];
+            L.state_base = s0;
+            L.arc_base = arc_offsets[s0];
+            L.ws_off = 0;
+            L.ref_base = static_cast<int64_t>(refw.size());
+            L.n_states = ns;
+            L.n_arcs = static_cast<int32_t>(arc_offsets[s0 + ns] - arc_offsets[s0]);
+            L.start = lat_start[l];
+            L.lat = l;
+            L.pad = 0;
+            for (int64_t i = ref_offsets[l]; i < ref_offsets[l + 1]; i++)
+              if (word(ref_words[i]) != 0) refw.push_back(ref_words[i]);
+            L.R = static_cast<int32_t>(static_cast<int64_t>(refw.size()) - L.ref_base);
+            return true;
+          },
+          [&](int, int64_t k, int64_t j) { in_label[k] = word(arc_label[j]); })) {
+    SetError("%s", err.c_str());
+    return KH_EINVAL;
   }
   // the lattices in flight: longest first, as many as the workspace limit admits per launch (at least one)
   auto cells = [&](const OrLat &L) { return static_cast<size_t>(L.n_states) * (static_cast<size_t>(L.R) + 1) * static_cast<size_t>(P); };
-  std::vector<int32_t> order(n_lats);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cells(lats[x]) > cells(lats[y]); });
   const int64_t path_total = path_offsets[static_cast<int64_t>(n_lats) * P];
-  size_t limit = g_workspace_limit;
-  if (limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if ((rc = kh_mem_info(&free_b, &total_b)) != KH_OK) return rc;
-    const size_t fixed = static_cast<size_t>(A) * (16 + (masked ? 8 * W : 0)) + static_cast<size_t>(S) * (16 + (masked ? 16 * W : 0)) +
-                         sizeof(int32_t) * (refw.size() + static_cast<size_t>(path_total)) + 48 * static_cast<size_t>(n_lats) * P;
-    const size_t avail = free_b + PoolCachedBytes();
-    limit = avail > 2 * fixed ? (avail - fixed) / 2 : avail / 4;
-  }
-  struct Chunk { int32_t begin, end; size_t ws_cells; };
-  std::vector<Chunk> chunks;
+  size_t limit = g_stats.workspace_limit;
+  if (limit == 0 &&
+      (rc = DefaultWorkspaceLimit(static_cast<size_t>(A) * (16 + (masked ? 8 * W : 0)) + static_cast<size_t>(S) * (16 + (masked ? 16 * W : 0)) +
+                                      sizeof(int32_t) * (refw.size() + static_cast<size_t>(path_total)) + 48 * static_cast<size_t>(n_lats) * P,
+                                  &limit)) != KH_OK)
+    return rc;
+  std::vector<size_t> ws_bytes(n_lats);
+  for (int l = 0; l < n_lats; l++) ws_bytes[l] = cells(lats[l]) * sizeof(int32_t);
+  const ChunkPlan plan = PlanChunks(ws_bytes, limit);
   std::vector<OrLat> sorted(n_lats);
   size_t max_ws_cells = 0;
-  for (int32_t i = 0; i < n_lats;) {
-    Chunk c{i, i, 0};
-    while (c.end < n_lats && c.end - c.begin < 65535) {
-      OrLat L = lats[order[c.end]];
-      const size_t b = cells(L);
-      if (c.end > c.begin && (c.ws_cells + b) * sizeof(int32_t) > limit) break;
-      L.ws_off = static_cast<int64_t>(c.ws_cells);
-      c.ws_cells += b;
-      sorted[c.end++] = L;
+  for (const ChunkRange &c : plan.ranges) {
+    size_t ws_cells = 0;
+    for (size_t i = c.begin; i < c.end; i++) {
+      sorted[i] = lats[plan.order[i]];
+      sorted[i].ws_off = static_cast<int64_t>(ws_cells);
+      ws_cells += cells(sorted[i]);
     }
-    max_ws_cells = std::max(max_ws_cells, c.ws_cells);
-    chunks.push_back(c);
-    i = c.end;
+    max_ws_cells = std::max(max_ws_cells, ws_cells);
   }
-  const auto t_host1 = std::chrono::steady_clock::now();
+  T.HostDone();
 
   hipStream_t st = Stream();
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  for (int i = 0; i < 4; i++) KH_HIP(hipEventCreate(&ev[i]));
+  KH_HIP(T.Init());
   Dev<OrLat> d_lats;
   Dev<int64_t> d_in_off, d_poff, d_fsum;
   Dev<int32_t> d_in_src, d_in_arc, d_in_label, d_refw, d_isfin, d_aframes, d_fframes, d_ws, d_err, d_cnt, d_plen, d_parcs, d_pfin;
@@ -410,28 +346,24 @@ extern "C" int kh_compact_lattice_oracle(int n_lats, const int32_t *lat_state_of
              static_cast<long long>(max_ws_cells));
     return KH_ENOMEM;
   }
-#define UP(dev, host, count, type) KH_HIP(hipMemcpyAsync(dev.p, host, sizeof(type) * (count), hipMemcpyHostToDevice, st))
-  KH_HIP(hipEventRecord(ev[0], st));
-  UP(d_lats, sorted.data(), n_lats, OrLat);
-  UP(d_in_off, in_off.data(), S + 1, int64_t);
-  UP(d_poff, path_offsets, LP + 1, int64_t);
-  UP(d_isfin, is_final, S, int32_t);
-  if (!refw.empty()) UP(d_refw, refw.data(), refw.size(), int32_t);
-  if (A > 0) {
-    UP(d_in_src, in_src.data(), A, int32_t);
-    UP(d_in_arc, in_arc.data(), A, int32_t);
-    UP(d_in_label, in_label.data(), A, int32_t);
-    if (frames) UP(d_aframes, arc_frames, A, int32_t);
-    if (masked) UP(d_ak, arc_keep, AW, uint64_t);
-  }
-  if (frames) UP(d_fframes, final_frames, S, int32_t);
+  KH_HIP(T.Mark(0, st));
+  KH_HIP(Up(d_lats, sorted.data(), n_lats, st));
+  KH_HIP(Up(d_in_off, in.in_off.data(), S + 1, st));
+  KH_HIP(Up(d_poff, path_offsets, LP + 1, st));
+  KH_HIP(Up(d_isfin, is_final, S, st));
+  KH_HIP(Up(d_refw, refw.data(), refw.size(), st));
+  KH_HIP(Up(d_in_src, in.in_src.data(), A, st));
+  KH_HIP(Up(d_in_arc, in.in_arc.data(), A, st));
+  KH_HIP(Up(d_in_label, in_label.data(), A, st));
+  if (frames) KH_HIP(Up(d_aframes, arc_frames, A, st));
+  if (masked) KH_HIP(Up(d_ak, arc_keep, AW, st));
+  if (frames) KH_HIP(Up(d_fframes, final_frames, S, st));
   if (masked) {
-    UP(d_sk, state_keep, SW, uint64_t);
-    UP(d_fk, final_keep, SW, uint64_t);
+    KH_HIP(Up(d_sk, state_keep, SW, st));
+    KH_HIP(Up(d_fk, final_keep, SW, st));
   }
-#undef UP
-  KH_HIP(hipEventRecord(ev[1], st));
-  for (const Chunk &c : chunks) {
+  KH_HIP(T.Mark(1, st));
+  for (const ChunkRange &c : plan.ranges) {
     hipLaunchKernelGGL(OracleKernel, dim3(c.end - c.begin, static_cast<unsigned>(P)), dim3(kLanes), 0, st, d_lats.p + c.begin,
                        d_in_off.p, d_in_src.p, d_in_arc.p, d_in_label.p, d_refw.p, d_isfin.p, masked ? d_ak.p : nullptr,
                        masked ? d_sk.p : nullptr, masked ? d_fk.p : nullptr, frames ? d_aframes.p : nullptr,
@@ -439,25 +371,18 @@ extern "C" int kh_compact_lattice_oracle(int n_lats, const int32_t *lat_state_of
                        d_parcs.p, d_poff.p, d_pfin.p, d_fsum.p);
     KH_LAUNCH_CHECK();
   }
-  KH_HIP(hipEventRecord(ev[2], st));
+  KH_HIP(T.Mark(2, st));
   KH_HIP(hipMemcpyAsync(errors, d_err.p, sizeof(int32_t) * LP, hipMemcpyDeviceToHost, st));
   KH_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(int32_t) * 4 * LP, hipMemcpyDeviceToHost, st));
   KH_HIP(hipMemcpyAsync(path_len, d_plen.p, sizeof(int32_t) * LP, hipMemcpyDeviceToHost, st));
   KH_HIP(hipMemcpyAsync(path_final_state, d_pfin.p, sizeof(int32_t) * LP, hipMemcpyDeviceToHost, st));
   if (path_total > 0) KH_HIP(hipMemcpyAsync(path_arcs, d_parcs.p, sizeof(int32_t) * path_total, hipMemcpyDeviceToHost, st));
   if (frames) KH_HIP(hipMemcpyAsync(arc_frame_sum, d_fsum.p, sizeof(int64_t) * LP, hipMemcpyDeviceToHost, st));
-  KH_HIP(hipEventRecord(ev[3], st));
+  KH_HIP(T.Mark(3, st));
   KH_HIP(hipStreamSynchronize(st));
-  float ms_up = 0.f, ms_kernel = 0.f, ms_down = 0.f;
-  KH_HIP(hipEventElapsedTime(&ms_up, ev[0], ev[1]));
-  KH_HIP(hipEventElapsedTime(&ms_kernel, ev[1], ev[2]));
-  KH_HIP(hipEventElapsedTime(&ms_down, ev[2], ev[3]));
-  g_ms[0] = std::chrono::duration<float, std::milli>(t_host1 - t_host0).count();
-  g_ms[1] = ms_up;
-  g_ms[2] = ms_kernel;
-  g_ms[3] = ms_down;
-  g_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-  g_calls = static_cast<int32_t>(chunks.size());
+  KH_HIP(T.AddAll());
+  T.Finish(g_stats.ms);
+  g_stats.counts[0] = static_cast<int32_t>(plan.ranges.size());
   for (size_t i = 0; i < LP; i++) {
     if (errors[i] == -2) {
       SetError("kh_compact_lattice_oracle: lattice %d, point %d: the walk back lost the path (internal error)",

@@ -1,7 +1,7 @@
 // kh_latprune.hip — PruneLattice<CompactLattice> (lat/lattice-functions.cc:186-265) for a batch of top-sorted
 // CompactLattices and K "score points" at once: what `lattice-scale | lattice-add-penalty | lattice-prune --beam=B` computes
 // once per point of the scoring grid (egs/tedlium/s5/local/score_sclite.sh and its relatives).  The score point is the one
-// of kh_latbest.hip (the ten lines that apply it to a weight are repeated here on purpose: that file holds one kernel).
+// of kh_latbest.hip; both take it from kh_scorepoint.h.
 //
 // Shape: one wave per (lattice, group of 64 points), lane = point.  The arc records are wave-uniform, the per-state row
 // cost[state][point] is contiguous across lanes, and every lane executes the reference's statements in the reference's
@@ -19,13 +19,13 @@
 // release / acquire).  A second, data-parallel kernel then forms arc_keep = keep & reach[src] & co[dst] and
 // state_keep = reach & co for the whole batch.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
-#include <numeric>
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_latbatch.h"
+#include "kh_scorepoint.h"
 
 namespace kh {
 namespace {
@@ -42,30 +42,6 @@ struct PrLat {
   int32_t lat;         // index in the caller's batch
   int32_t pad;
 };
-
-struct Point {
-  double s00, s01, s10, s11;
-  float pen;
-};
-
-// ScaleTupleWeight fstext/lattice-weight.h:233-241: Zero stays Zero (:237-238); products and sums in double, the
-// LatticeWeightTpl<float> constructor narrows.
-__device__ __forceinline__ void ScaleWeight(float g, float a, const Point &pt, float *g2, float *a2) {
-  if (g == INFINITY) {
-    *g2 = INFINITY;
-    *a2 = INFINITY;
-  } else {
-    *g2 = static_cast<float>(pt.s00 * static_cast<double>(g) + pt.s01 * static_cast<double>(a));
-    *a2 = static_cast<float>(pt.s10 * static_cast<double>(g) + pt.s11 * static_cast<double>(a));
-  }
-}
-// ... followed by AddWordInsPenToCompactLattice lat/lattice-functions.cc:1140-1143 (float sum, arcs with a word only)
-__device__ __forceinline__ void ArcWeight(float g, float a, int32_t label, const Point &pt, float *g2, float *a2) {
-  ScaleWeight(g, a, pt, g2, a2);
-  if (label != 0) *g2 = *g2 + pt.pen;
-}
-// ConvertToCost fstext/lattice-weight.h:799-801
-__device__ __forceinline__ double Cost(float g2, float a2) { return static_cast<double>(g2) + static_cast<double>(a2); }
 
 // a mask word written by lane 0 and read by every lane of the same wave later in program order
 __device__ __forceinline__ void PutWord(uint64_t *p, uint64_t v) {
@@ -89,12 +65,7 @@ __global__ __launch_bounds__(kLanes) void PruneKernel(
   const bool valid = w * kLanes + lane < n_points;
   const int p = valid ? w * kLanes + lane : n_points - 1;
   const uint64_t live = __ballot(valid);
-  Point pt;
-  pt.s00 = scales[4 * p];
-  pt.s01 = scales[4 * p + 1];
-  pt.s10 = scales[4 * p + 2];
-  pt.s11 = scales[4 * p + 3];
-  pt.pen = penalties[p];
+  const Point pt = LoadPoint(scales, penalties, p);
   const int64_t PP = static_cast<int64_t>(n_words) * kLanes, W = n_words;
   double *c = cost + L.ws_row * PP + w * kLanes + lane;
   const int64_t *io = in_off + L.state_base, *ao = arc_off + L.state_base;
@@ -178,19 +149,7 @@ __global__ __launch_bounds__(kFinishThreads) void PruneFinishKernel(
   }
 }
 
-template <typename T>
-struct Dev {
-  T *p = nullptr;
-  ~Dev() { if (p) PoolFree(p); }
-  int Alloc(size_t n) {
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * (n ? n : 1)));
-    return p ? KH_OK : KH_ENOMEM;
-  }
-};
-
-thread_local float g_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-thread_local int32_t g_calls = 0;            // PruneKernel launches of the last call
-thread_local size_t g_workspace_limit = 0;   // of the calling thread; 0: from kh_mem_info
+thread_local CallStats<5, 1> g_stats;   // counts: PruneKernel launches of the last call
 
 // NaN and -inf make a min sweep depend on the order of its candidates
 inline bool BadWeight(float x) { return std::isnan(x) || x == -std::numeric_limits<float>::infinity(); }
@@ -201,15 +160,12 @@ inline bool BadWeight(float x) { return std::isnan(x) || x == -std::numeric_limi
 using namespace kh;
 
 extern "C" int kh_compact_lattice_prune_set_workspace_limit(size_t bytes) {
-  g_workspace_limit = bytes;
+  g_stats.workspace_limit = bytes;
   return KH_OK;
 }
 
 extern "C" int kh_compact_lattice_prune_last_timings(float *ms5, int32_t *n_launches) {
-  KH_CHECK_ARG(ms5);
-  for (int i = 0; i < 5; i++) ms5[i] = g_ms[i];
-  if (n_launches) *n_launches = g_calls;
-  return KH_OK;
+  return GetTimings(g_stats, ms5, n_launches);
 }
 
 extern "C" int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_offsets, const int32_t *lat_start,
@@ -229,7 +185,7 @@ extern "C" int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_off
                final_keep && best_final_cost);
   KH_CHECK_ARG(lat_state_offsets[0] == 0 && arc_offsets[0] == 0);
   for (int l = 0; l < n_lats; l++) KH_CHECK_ARG(lat_state_offsets[l + 1] - lat_state_offsets[l] > 0);
-  const auto t_host0 = std::chrono::steady_clock::now();
+  CallTimer T;
   const int64_t S = lat_state_offsets[n_lats], A = arc_offsets[S];
   KH_CHECK_ARG(A >= 0 && A < (1ll << 31));   // (arc positions within a lattice are kept as int32 in the incoming lists)
   const int64_t P = n_points, W = (P + kLanes - 1) / kLanes;
@@ -241,7 +197,10 @@ extern "C" int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_off
   }
 
   // validation (:193, :218: every arc goes to a higher-numbered state of its own lattice; the weights) and the incoming
-  // lists: a counting sort by destination, which keeps the arcs of one destination in (source state, arc position) order
+  // lists: a counting sort by destination, which keeps the arcs of one destination in (source state, arc position) order.
+  // This walk and the planner below are BuildIncoming and PlanChunks of kh_latbatch_host.h written out: a call here prepares
+  // 64 small lattices in 8 us, and through the shared walker's hooks it measured about 1 us slower
+  // (profiles/latbatch_refactor_ab.json).  A change to either belongs in both.
   std::vector<int64_t> in_off(S + 1, 0);
   std::vector<PrLat> lats(n_lats);
   for (int l = 0; l < n_lats; l++) {
@@ -307,14 +266,10 @@ extern "C" int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_off
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return lats[x].n_states > lats[y].n_states; });
   const size_t row_bytes = sizeof(double) * kLanes * static_cast<size_t>(W);
-  size_t limit = g_workspace_limit;
-  if (limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if ((rc = kh_mem_info(&free_b, &total_b)) != KH_OK) return rc;
-    const size_t fixed = static_cast<size_t>(A) * (36 + 8 * W) + static_cast<size_t>(S) * (24 + 32 * W);
-    const size_t avail = free_b + PoolCachedBytes();
-    limit = avail > 2 * fixed ? (avail - fixed) / 2 : avail / 4;
-  }
+  size_t limit = g_stats.workspace_limit;
+  if (limit == 0 && (rc = DefaultWorkspaceLimit(static_cast<size_t>(A) * (36 + 8 * W) + static_cast<size_t>(S) * (24 + 32 * W),
+                                                &limit)) != KH_OK)
+    return rc;
   struct Chunk { int32_t begin, end; int64_t ws_rows; };
   std::vector<Chunk> chunks;
   std::vector<PrLat> sorted(n_lats);
@@ -335,12 +290,10 @@ extern "C" int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_off
     chunks.push_back(c);
     i = c.end;
   }
-  const auto t_host1 = std::chrono::steady_clock::now();
+  T.HostDone();
 
   hipStream_t st = Stream();
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  for (int i = 0; i < 4; i++) KH_HIP(hipEventCreate(&ev[i]));
+  KH_HIP(T.Init());
   Dev<PrLat> d_lats;
   Dev<int64_t> d_in_off, d_arc_off;
   Dev<int32_t> d_in_src, d_in_arc, d_in_label, d_label, d_next;
@@ -357,29 +310,25 @@ extern "C" int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_off
              static_cast<long long>(max_ws_rows), static_cast<long long>(kLanes * W));
     return KH_ENOMEM;
   }
-#define UP(dev, host, count, type) KH_HIP(hipMemcpyAsync(dev.p, host, sizeof(type) * (count), hipMemcpyHostToDevice, st))
-  KH_HIP(hipEventRecord(ev[0], st));
-  UP(d_lats, sorted.data(), n_lats, PrLat);
-  UP(d_in_off, in_off.data(), S + 1, int64_t);
-  UP(d_arc_off, arc_offsets, S + 1, int64_t);
-  if (A > 0) {
-    UP(d_in_src, in_src.data(), A, int32_t);
-    UP(d_in_arc, in_arc.data(), A, int32_t);
-    UP(d_in_label, in_label.data(), A, int32_t);
-    UP(d_in_g, in_g.data(), A, float);
-    UP(d_in_a, in_a.data(), A, float);
-    UP(d_label, arc_label, A, int32_t);
-    UP(d_next, arc_nextstate, A, int32_t);
-    UP(d_g, arc_graph, A, float);
-    UP(d_a, arc_acoustic, A, float);
-  }
-  UP(d_fin_g, final_graph, S, float);
-  UP(d_fin_a, final_acoustic, S, float);
-  UP(d_scales, scales, 4 * P, double);
-  UP(d_pen, penalties, P, float);
-  UP(d_beam, beams, P, float);
-#undef UP
-  KH_HIP(hipEventRecord(ev[1], st));
+  KH_HIP(T.Mark(0, st));
+  KH_HIP(Up(d_lats, sorted.data(), n_lats, st));
+  KH_HIP(Up(d_in_off, in_off.data(), S + 1, st));
+  KH_HIP(Up(d_arc_off, arc_offsets, S + 1, st));
+  KH_HIP(Up(d_in_src, in_src.data(), A, st));
+  KH_HIP(Up(d_in_arc, in_arc.data(), A, st));
+  KH_HIP(Up(d_in_label, in_label.data(), A, st));
+  KH_HIP(Up(d_in_g, in_g.data(), A, st));
+  KH_HIP(Up(d_in_a, in_a.data(), A, st));
+  KH_HIP(Up(d_label, arc_label, A, st));
+  KH_HIP(Up(d_next, arc_nextstate, A, st));
+  KH_HIP(Up(d_g, arc_graph, A, st));
+  KH_HIP(Up(d_a, arc_acoustic, A, st));
+  KH_HIP(Up(d_fin_g, final_graph, S, st));
+  KH_HIP(Up(d_fin_a, final_acoustic, S, st));
+  KH_HIP(Up(d_scales, scales, 4 * P, st));
+  KH_HIP(Up(d_pen, penalties, P, st));
+  KH_HIP(Up(d_beam, beams, P, st));
+  KH_HIP(T.Mark(1, st));
   for (const Chunk &c : chunks) {
     hipLaunchKernelGGL(PruneKernel, dim3(c.end - c.begin, static_cast<unsigned>(W)), dim3(kLanes), 0, st, d_lats.p + c.begin,
                        d_in_off.p, d_in_src.p, d_in_arc.p, d_in_label.p, d_in_g.p, d_in_a.p, d_arc_off.p, d_label.p, d_next.p,
@@ -390,22 +339,15 @@ extern "C" int kh_compact_lattice_prune(int n_lats, const int32_t *lat_state_off
                        d_next.p, static_cast<int>(W), d_co.p, d_reach.p, d_keep.p, d_sk.p);
     KH_LAUNCH_CHECK();
   }
-  KH_HIP(hipEventRecord(ev[2], st));
+  KH_HIP(T.Mark(2, st));
   if (A > 0) KH_HIP(hipMemcpyAsync(arc_keep, d_keep.p, sizeof(uint64_t) * AW, hipMemcpyDeviceToHost, st));
   KH_HIP(hipMemcpyAsync(state_keep, d_sk.p, sizeof(uint64_t) * SW, hipMemcpyDeviceToHost, st));
   KH_HIP(hipMemcpyAsync(final_keep, d_fk.p, sizeof(uint64_t) * SW, hipMemcpyDeviceToHost, st));
   KH_HIP(hipMemcpyAsync(best_final_cost, d_best.p, sizeof(double) * LP, hipMemcpyDeviceToHost, st));
-  KH_HIP(hipEventRecord(ev[3], st));
+  KH_HIP(T.Mark(3, st));
   KH_HIP(hipStreamSynchronize(st));
-  float ms_up = 0.f, ms_kernel = 0.f, ms_down = 0.f;
-  KH_HIP(hipEventElapsedTime(&ms_up, ev[0], ev[1]));
-  KH_HIP(hipEventElapsedTime(&ms_kernel, ev[1], ev[2]));
-  KH_HIP(hipEventElapsedTime(&ms_down, ev[2], ev[3]));
-  g_ms[0] = std::chrono::duration<float, std::milli>(t_host1 - t_host0).count();
-  g_ms[1] = ms_up;
-  g_ms[2] = ms_kernel;
-  g_ms[3] = ms_down;
-  g_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-  g_calls = static_cast<int32_t>(chunks.size());
+  KH_HIP(T.AddAll());
+  T.Finish(g_stats.ms);
+  g_stats.counts[0] = static_cast<int32_t>(chunks.size());
   return KH_OK;
 }

@@ -15,11 +15,11 @@
 // Which items go where is decided per item on the host (len > kShortLen), which builds the list of long items while it
 // computes the state times.  Both kernels add in the same order, so the cut-over changes no bit.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <vector>
 
 #include "kh_common.h"
+#include "kh_latbatch.h"
 
 namespace kh {
 namespace {
@@ -86,18 +86,7 @@ __global__ __launch_bounds__(kThreads) void RescoreLongKernel(Items I, const int
   if (lane == 0) val[j] = v;
 }
 
-template <typename T>
-struct Dev {
-  T *p = nullptr;
-  ~Dev() { if (p) PoolFree(p); }
-  int Alloc(size_t n) {
-    p = static_cast<T *>(PoolMalloc(sizeof(T) * (n ? n : 1)));
-    return p ? KH_OK : KH_ENOMEM;
-  }
-};
-
-thread_local float g_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-thread_local int32_t g_counts[3] = {0, 0, 0};
+thread_local CallStats<5, 3> g_stats;   // counts: launches, short items, long items
 
 }  // namespace
 }  // namespace kh
@@ -105,10 +94,7 @@ thread_local int32_t g_counts[3] = {0, 0, 0};
 using namespace kh;
 
 extern "C" int kh_rescore_compact_lattice_last_timings(float *ms5, int32_t *counts3) {
-  KH_CHECK_ARG(ms5);
-  for (int i = 0; i < 5; i++) ms5[i] = g_ms[i];
-  if (counts3) for (int i = 0; i < 3; i++) counts3[i] = g_counts[i];
-  return KH_OK;
+  return GetTimings(g_stats, ms5, counts3);
 }
 
 extern "C" int kh_rescore_compact_lattice(
@@ -127,7 +113,7 @@ extern "C" int kh_rescore_compact_lattice(
   for (int l = 0; l < n_lats; l++)
     KH_CHECK_ARG(lat_state_offsets[l + 1] >= lat_state_offsets[l] && ll_row_offsets[l + 1] >= ll_row_offsets[l]);
   KH_CHECK_ARG(ll_row_offsets[n_lats] <= d_loglikes.rows);
-  const auto t_host0 = std::chrono::steady_clock::now();
+  CallTimer T;
   const int64_t S = lat_state_offsets[n_lats];
   for (int64_t s = 0; s < S; s++)
     KH_CHECK_ARG(arc_offsets[s + 1] >= arc_offsets[s] && final_string_offsets[s + 1] >= final_string_offsets[s] &&
@@ -145,6 +131,7 @@ extern "C" int kh_rescore_compact_lattice(
   const float inf = INFINITY;
   std::vector<int32_t> times, arc_row(A, -1), final_row(S, -1);
   std::vector<int64_t> long_items;
+  std::string err;
   int64_t n_short = 0;
   for (int l = 0; l < n_lats; l++) {
     const int32_t s0 = lat_state_offsets[l], ns = lat_state_offsets[l + 1] - s0;
@@ -157,10 +144,8 @@ extern "C" int kh_rescore_compact_lattice(
     // kTopSorted (:1173; the caller sorts as fst::TopSort does)
     for (int32_t s = 0; s < ns; s++) {
       for (int64_t j = arc_offsets[s0 + s]; j < arc_offsets[s0 + s + 1]; j++) {
-        const int32_t nx = arc_nextstate[j];
-        if (nx <= s || nx >= ns) {
-          SetError("kh_rescore_compact_lattice: lattice %d: arc %lld (state %d -> %d of %d): input lattice must be "
-                   "topologically sorted", l, static_cast<long long>(j - a0), s, nx, ns);
+        if (!ForwardArc("kh_rescore_compact_lattice", l, j - a0, s, arc_nextstate[j], ns, &err)) {
+          SetError("%s", err.c_str());
           return KH_EINVAL;
         }
       }
@@ -249,21 +234,15 @@ extern "C" int kh_rescore_compact_lattice(
     (void)a1;
   }
   const int64_t n_long = static_cast<int64_t>(long_items.size());
-  const auto t_host1 = std::chrono::steady_clock::now();
-  g_ms[0] = std::chrono::duration<float, std::milli>(t_host1 - t_host0).count();
-  g_ms[1] = g_ms[2] = g_ms[3] = 0.f;
-  g_counts[0] = 0;
-  g_counts[1] = static_cast<int32_t>(std::min<int64_t>(n_short, INT32_MAX));
-  g_counts[2] = static_cast<int32_t>(std::min<int64_t>(n_long, INT32_MAX));
-  if (n_short + n_long == 0) {   // nothing owns a frame: every cost keeps its bits
-    g_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-    return KH_OK;
-  }
+  T.HostDone();
+  T.Finish(g_stats.ms);
+  g_stats.counts[0] = 0;
+  g_stats.counts[1] = static_cast<int32_t>(std::min<int64_t>(n_short, INT32_MAX));
+  g_stats.counts[2] = static_cast<int32_t>(std::min<int64_t>(n_long, INT32_MAX));
+  if (n_short + n_long == 0) return KH_OK;   // nothing owns a frame: every cost keeps its bits
 
   hipStream_t st = Stream();
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  for (int i = 0; i < 4; i++) KH_HIP(hipEventCreate(&ev[i]));
+  KH_HIP(T.Init());
   Dev<int64_t> d_arc_off, d_final_off, d_long;
   Dev<int32_t> d_strings, d_arc_row, d_final_row, d_t2p;
   Dev<float> d_arc_a, d_final_a;
@@ -273,20 +252,17 @@ extern "C" int kh_rescore_compact_lattice(
              static_cast<long long>(n_strings));
     return KH_ENOMEM;
   }
-#define UP(dev, host, count, type) \
-  if ((count) > 0) KH_HIP(hipMemcpyAsync(dev.p, host, sizeof(type) * (count), hipMemcpyHostToDevice, st))
-  KH_HIP(hipEventRecord(ev[0], st));
-  UP(d_arc_off, arc_string_offsets, A + 1, int64_t);
-  UP(d_final_off, final_string_offsets, S + 1, int64_t);
-  UP(d_long, long_items.data(), n_long, int64_t);
-  UP(d_strings, strings, n_strings, int32_t);
-  UP(d_arc_row, arc_row.data(), A, int32_t);
-  UP(d_final_row, final_row.data(), S, int32_t);
-  UP(d_t2p, tid2pdf, num_tids + 1, int32_t);
-  UP(d_arc_a, arc_acoustic, A, float);
-  UP(d_final_a, final_acoustic, S, float);
-#undef UP
-  KH_HIP(hipEventRecord(ev[1], st));
+  KH_HIP(T.Mark(0, st));
+  KH_HIP(Up(d_arc_off, arc_string_offsets, A + 1, st));
+  KH_HIP(Up(d_final_off, final_string_offsets, S + 1, st));
+  KH_HIP(Up(d_long, long_items.data(), n_long, st));
+  KH_HIP(Up(d_strings, strings, n_strings, st));
+  KH_HIP(Up(d_arc_row, arc_row.data(), A, st));
+  KH_HIP(Up(d_final_row, final_row.data(), S, st));
+  KH_HIP(Up(d_t2p, tid2pdf, num_tids + 1, st));
+  KH_HIP(Up<float>(d_arc_a, arc_acoustic, A, st));
+  KH_HIP(Up<float>(d_final_a, final_acoustic, S, st));
+  KH_HIP(T.Mark(1, st));
   Items I;
   I.arc_off = d_arc_off.p;
   I.final_off = d_final_off.p;
@@ -315,15 +291,13 @@ extern "C" int kh_rescore_compact_lattice(
     launches++;
     done += n;
   }
-  KH_HIP(hipEventRecord(ev[2], st));
+  KH_HIP(T.Mark(2, st));
   if (A > 0) KH_HIP(hipMemcpyAsync(arc_acoustic, d_arc_a.p, sizeof(float) * A, hipMemcpyDeviceToHost, st));
   if (S > 0) KH_HIP(hipMemcpyAsync(final_acoustic, d_final_a.p, sizeof(float) * S, hipMemcpyDeviceToHost, st));
-  KH_HIP(hipEventRecord(ev[3], st));
+  KH_HIP(T.Mark(3, st));
   KH_HIP(hipStreamSynchronize(st));
-  KH_HIP(hipEventElapsedTime(&g_ms[1], ev[0], ev[1]));
-  KH_HIP(hipEventElapsedTime(&g_ms[2], ev[1], ev[2]));
-  KH_HIP(hipEventElapsedTime(&g_ms[3], ev[2], ev[3]));
-  g_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-  g_counts[0] = launches;
+  KH_HIP(T.AddAll());
+  T.Finish(g_stats.ms);
+  g_stats.counts[0] = launches;
   return KH_OK;
 }

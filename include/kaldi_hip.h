@@ -1319,6 +1319,45 @@ int kh_fmllr_set_workspace_limit(size_t bytes);
  * kernels alone (device events), and the number of speaker groups B took. */
 int kh_fmllr_last_timings(float *ms);
 
+/* ------------------------------------------------------------------ GMM training statistics (csrc/kh_gmmacc.hip)
+ * The E-step of gmm-acc-stats-ali / gmm-acc-stats / gmm-acc-stats-twofeats for a batch of stacked frames: for given Gaussian
+ * posteriors (kh_gmm_acc_component_posteriors below, stage A1 above, or any given ones) AccumDiagGmm::AccumulateFromPosteriors (gmm/mle-diag-gmm.cc:171-189) under
+ * AccumulateFromDiag (:191-204) under AccumAmDiagGmm::AccumulateForGmm / AccumulateForGmmTwofeats
+ * (gmm/mle-am-diag-gmm.cc:69-97).  Per Gaussian g of each pdf, in double, over the entries e that name the pdf:
+ *     occ[g] += p[e, g],   mean_acc[g, d] += p[e, g] x[row(e), d],   var_acc[g, d] += p[e, g] x[row(e), d]^2,
+ * p the float posterior (already times the entry's weight) and x the float feature row, both widened first.  feats (DEVICE,
+ * T x D, row pitch feat_stride) are the features the STATISTICS are taken from: their D need not be the model's (the
+ * two-feature route).  The entry list is A1's (HOST), gauss_post DEVICE.  flags: kGmmMeans 1 | kGmmVariances 2 | kGmmWeights 4
+ * after AugmentGmmFlags (gmm/model-common.cc:52-61: v needs m, m needs w); an accumulator the flags exclude is not touched
+ * and may be NULL.  HOST outputs occ [NG], mean_acc, var_acc [NG x D] (NG = pdf_offsets[num_pdfs]) are SET, not added to; a
+ * pdf no entry names gets zeros; T = 0 or no entries: zeros.  Every index is checked on the host before a launch (KH_EINVAL
+ * naming the pdf or entry).  The entries are sorted by pdf (stable: frame order within a pdf) and a pdf's run is cut into
+ * chunks of kh_gmm_acc_chunk entries; per pdf an fp64 matrix-core GEMM P^T [1 | X | X o X] with the right operand made on the
+ * fly, partial sums per chunk added in chunk order, no atomics: the same input gives the same bits.  The sum order is this
+ * chunk tree's, not the reference's BLAS order.  D = 1 ... kh_gmm_acc_max_dim (127); above: KH_EINVAL before any launch.
+ * total_log_like_ / total_frames_ (mle-am-diag-gmm.cc:76-77) are host sums over the posteriors call's entry_like, left to the caller. */
+int kh_gmm_acc_stats(const float *feats, int T, int D, int feat_stride, const int32_t *pdf_offsets, int num_pdfs,
+                     const int64_t *frame_entry_offsets, const int32_t *entry_pdf, const int64_t *entry_gauss_offsets,
+                     const float *gauss_post, int flags, double *occ, double *mean_acc, double *var_acc);
+/* The Gaussian posteriors of this route: kh_gmm_component_posteriors' arguments, checks and arithmetic (stage A1 above), with
+ * EXP and LOG as fl32 of the double function (the device library's double exp / log, under 1 ulp in double), which is how the
+ * line-by-line restatement of DiagGmm::ComponentPosteriors states them, where A1 takes the device library's expf / logf (1 ulp in
+ * float).  The checks are those of kh_gmm_acc_stats (csrc/kh_gmmacc_plan.h).  The statistics go to a file as floats: with 1-ulp
+ * posteriors a mean accumulator whose addends cancel moves by several float ulps, with these it does not. */
+int kh_gmm_acc_component_posteriors(const float *feats, int T, int D, int feat_stride, const float *gconsts,
+                                    const float *means_invvars, const float *inv_vars, const int32_t *pdf_offsets, int num_pdfs,
+                                    const int64_t *frame_entry_offsets, const int32_t *entry_pdf, const float *entry_weight,
+                                    const int64_t *entry_gauss_offsets, float *gauss_post, float *entry_like);
+int kh_gmm_acc_chunk(void);
+int kh_gmm_acc_max_dim(void);
+/* The pdfs go in groups whose workspace ((chunks + 1) x Gaussians x columns doubles per pdf: a partial sum per chunk and the
+ * sum) stays within this many bytes (calling thread; 0 = the default, 1 GiB); a pdf is never split.  No sum depends on it. */
+int kh_gmm_acc_set_workspace_limit(size_t bytes);
+/* ms[4]: milliseconds of the calling thread's last kh_gmm_acc_stats: the whole call, its host plan (checks, sort, groups), its
+ * two kernels alone (device events); then of its last kh_gmm_acc_component_posteriors (whole call).  counts[3]: pdf groups,
+ * chunks, workgroups of the accumulation kernel. */
+int kh_gmm_acc_last_timings(float *ms, int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3170,6 +3170,10 @@ def _entry_ptrs(ent, T):
 def gmm_component_posteriors(am, feats, ent):
     """DiagGmm::ComponentPosteriors (gmm/diag-gmm.cc:601-615) times the entry's weight, per entry (kh_gmm_component_posteriors).
     am: AmDiagGmm; feats: 2-D float32 device tensor.  Returns (gauss_post, like): device tensors of goff[E] and E floats."""
+    return _component_posteriors(lib().kh_gmm_component_posteriors, am, feats, ent)
+
+
+def _component_posteriors(entry, am, feats, ent):
     T, D, stride = _feat_args(feats)
     if D != am.dim:
         raise KhError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (D, am.dim))
@@ -3181,9 +3185,9 @@ def gmm_component_posteriors(am, feats, ent):
     post = torch.zeros(max(int(goff[-1]), 1), dtype=torch.float32, device=feats.device)
     like = torch.zeros(max(len(pdf), 1), dtype=torch.float32, device=feats.device)
     ip, lp = capi.c_int32_p, capi.c_int64_p
-    check(lib().kh_gmm_component_posteriors(_p(feats), T, D, stride, _p(am.gconsts), _p(am.means_invvars), _p(am.inv_vars),
-                                            off.ctypes.data_as(ip), am.num_pdfs, feo.ctypes.data_as(lp), pdf.ctypes.data_as(ip),
-                                            w.ctypes.data_as(capi.c_float_p), goff.ctypes.data_as(lp), _p(post), _p(like)))
+    check(entry(_p(feats), T, D, stride, _p(am.gconsts), _p(am.means_invvars), _p(am.inv_vars), off.ctypes.data_as(ip), am.num_pdfs,
+                feo.ctypes.data_as(lp), pdf.ctypes.data_as(ip), w.ctypes.data_as(capi.c_float_p), goff.ctypes.data_as(lp), _p(post),
+                _p(like)))
     return post[:int(goff[-1])], like[:len(pdf)]
 
 
@@ -3336,6 +3340,132 @@ def gmm_post_to_gpost(am, feats, pdf_posts):
                 fr.append((int(ent["pdf"][e]), v.copy()))
         out.append(fr)
     return out, like, ent["weight"]
+
+
+# ---------------------------------------------------------------- GMM training statistics (csrc/kh_gmmacc.hip)
+# The E-step of gmm-acc-stats-ali / gmm-acc-stats / gmm-acc-stats-twofeats for stacked frames, over the entry lists above.
+kGmmMeans, kGmmVariances, kGmmWeights, kGmmTransitions, kGmmAll = 1, 2, 4, 8, 15
+
+
+def gmm_flags(flags):
+    """StringToGmmFlags then AugmentGmmFlags (gmm/model-common.cc:26-61), as AccumDiagGmm::Resize stores them and Write emits
+    them: "mvwt" and kGmmAll -> 15 (the transition bit is kept: it is in the file), "mvw" and "v" -> 7, "m" -> 5, "" -> 4.  An
+    int is taken as the reference's bits."""
+    if isinstance(flags, str):
+        bits = 0
+        for c in flags:
+            if c not in "mvwta":
+                raise KhError("Invalid element '%s' of GmmFlagsType option string %s" % (c, flags))
+            bits |= {"m": kGmmMeans, "v": kGmmVariances, "w": kGmmWeights, "t": kGmmTransitions, "a": kGmmAll}[c]
+    else:
+        bits = int(flags)
+        if bits & ~kGmmAll:
+            raise KhError("AugmentGmmFlags: (flags & ~kGmmAll) == 0, got %d" % bits)
+    if bits & kGmmVariances:
+        bits |= kGmmMeans
+    return bits | kGmmWeights             # m needs w; and w is added to empty flags (with a warning in the reference)
+
+
+def gmm_flags_to_string(bits):
+    return "".join(c for c, b in (("m", 1), ("v", 2), ("w", 4), ("t", 8)) if bits & b)
+
+
+def gmm_acc_component_posteriors(am, feats, ent):
+    """gmm_component_posteriors with exp and log as the float of the double function (kh_gmm_acc_component_posteriors): the
+    posteriors of the accumulation route, whose sums are written to a file as floats."""
+    return _component_posteriors(lib().kh_gmm_acc_component_posteriors, am, feats, ent)
+
+
+def gmm_acc_stats(am, feats, ent, gauss_post, flags="mvw"):
+    """AccumDiagGmm::AccumulateFromPosteriors for every entry (kh_gmm_acc_stats).  am: AmDiagGmm (its pdf sizes are what is
+    used); feats: the 2-D float32 device tensor the statistics are taken from, of any dimension up to gmm_acc_max_dim();
+    gauss_post: the entries' Gaussian posteriors, float32 device tensor (gmm_acc_component_posteriors' output).  Returns
+    dict(occ [NG], mean_acc [NG, D], var_acc [NG, D]) float64 host arrays; an accumulator the flags exclude is None.  The
+    library call takes the m | v | w bits; the transition bit means nothing to it."""
+    bits = gmm_flags(flags)
+    T, D, stride = _feat_args(feats)
+    feo, pdf, goff = _entry_ptrs(ent, T)
+    if gauss_post.dtype != torch.float32 or not gauss_post.is_cuda or gauss_post.numel() != int(goff[-1]):
+        raise KhError("gmm_acc_stats: %d Gaussian posteriors for entries that hold %d" % (gauss_post.numel(), int(goff[-1])))
+    gauss_post = gauss_post.contiguous()
+    off = _host_pdf_offsets(am)
+    NG = int(off[-1])
+    occ = np.zeros(NG, np.float64)
+    mean = np.zeros((NG, D), np.float64) if bits & kGmmMeans else None
+    var = np.zeros((NG, D), np.float64) if bits & kGmmVariances else None
+    ip, lp, dp = capi.c_int32_p, capi.c_int64_p, capi.c_double_p
+    check(lib().kh_gmm_acc_stats(_p(feats), T, D, stride, off.ctypes.data_as(ip), am.num_pdfs, feo.ctypes.data_as(lp),
+                                 pdf.ctypes.data_as(ip), goff.ctypes.data_as(lp), _p(gauss_post), bits & 7, occ.ctypes.data_as(dp),
+                                 mean.ctypes.data_as(dp) if mean is not None else None,
+                                 var.ctypes.data_as(dp) if var is not None else None))
+    return dict(occ=occ, mean_acc=mean, var_acc=var)
+
+
+def gmm_acc_chunk():
+    """Entries per chunk of the accumulation kernel (kChunk of csrc/kh_gmmacc.hip)."""
+    return int(lib().kh_gmm_acc_chunk())
+
+
+def gmm_acc_max_dim():
+    return int(lib().kh_gmm_acc_max_dim())
+
+
+def gmm_acc_set_workspace_limit(nbytes):
+    """gmm_acc_stats takes the pdfs in groups whose workspace stays within nbytes (calling thread; 0 = 1 GiB)."""
+    check(lib().kh_gmm_acc_set_workspace_limit(int(nbytes)))
+
+
+def gmm_acc_last_timings():
+    """The calling thread's last gmm_acc_stats: milliseconds of the call, its host plan and its kernels, and of the last
+    gmm_acc_component_posteriors; groups, chunks, workgroups."""
+    return _timings(lib().kh_gmm_acc_last_timings, ("call_ms", "plan_ms", "kernels_ms", "component_posteriors_ms"),
+                    ("groups", "chunks", "workgroups"))
+
+
+def accumulate_gmm_stats(am, feats, pdf_posts=None, alignments=None, tid2pdf=None, stats_feats=None, flags="mvw", into=None,
+                         return_entries=False):
+    """gmm_acc_component_posteriors on feats, then gmm_acc_stats on stats_feats or feats:
+    AccumAmDiagGmm::AccumulateForGmm (mle-am-diag-gmm.cc:69-79) for every (frame, pdf, weight) of the stacked frames, or
+    AccumulateForGmmTwofeats (:81-97) when stats_feats is given: the posteriors from feats, the statistics from stats_feats
+    (the same rows, any dimension).  pdf_posts: [(pdf, weight), ...] per frame; or alignments (a transition-id per frame) with
+    tid2pdf, every weight 1.  total_like adds fl32(like * weight) and total_frames the weight, doubles in entry order (:76-77).
+    into: a dict this function returned, added to in double (pdf_offsets, dim and flags must agree).  Returns
+    dict(occ, mean_acc, var_acc, pdf_offsets, dim, flags, total_like, total_frames); flags are the augmented GmmFlagsType as the
+    file holds it ("mvwt" and kGmmAll: 15).  return_entries: also the entry list and the entries' scores (host float32), for a
+    caller's per-utterance figures: (accumulator, ent, like)."""
+    if (pdf_posts is None) == (alignments is None):
+        raise KhError("accumulate_gmm_stats: give pdf_posts or alignments")
+    off = _host_pdf_offsets(am)
+    if pdf_posts is None:
+        if tid2pdf is None:
+            raise KhError("accumulate_gmm_stats: alignments need tid2pdf")
+        pdf_posts = [[(int(tid2pdf[int(t)]), 1.0)] for t in alignments]
+    bits = gmm_flags(flags)
+    x2 = feats if stats_feats is None else stats_feats
+    if int(x2.shape[0]) != int(feats.shape[0]):
+        raise KhError("Features have mismatched numbers of frames %d vs. %d" % (feats.shape[0], x2.shape[0]))
+    ent = fmllr_entries(pdf_posts, off)
+    if len(ent["pdf"]):
+        post, like = gmm_acc_component_posteriors(am, feats, ent)
+        like = like.cpu().numpy()
+    else:
+        post, like = torch.zeros(0, dtype=torch.float32, device=feats.device), np.zeros(0, np.float32)
+    acc = gmm_acc_stats(am, x2, ent, post, bits)
+    # np.cumsum adds in order: the doubles of fl32(like * weight) and of the weights, entry by entry
+    tot_like = float(np.cumsum((like * ent["weight"]).astype(np.float64))[-1]) if len(like) else 0.0
+    tot_frames = float(np.cumsum(ent["weight"].astype(np.float64))[-1]) if len(like) else 0.0
+    acc.update(pdf_offsets=off, dim=int(x2.shape[1]), flags=bits, total_like=tot_like, total_frames=tot_frames)
+    acc = acc if into is None else add_gmm_stats(into, acc)
+    return (acc, ent, like) if return_entries else acc
+
+
+def add_gmm_stats(into, acc):
+    """into += acc in double, with the checks (and messages) of AccumAmDiagGmm::Read / AccumDiagGmm::Read with add = true."""
+    from . import kaldi_io
+    try:
+        return kaldi_io.add_gmm_accs(into, acc)
+    except ValueError as e:
+        raise KhError(str(e))
 
 
 # ---- host posterior / transform algebra of the fMLLR recipes

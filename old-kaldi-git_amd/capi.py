@@ -254,6 +254,14 @@ SIGNATURES = {
     "kh_fmllr_max_dim": (C.c_int, []),
     "kh_fmllr_frame_chunk": (C.c_int, []),
     "kh_fmllr_last_timings": (C.c_int, [c_float_p]),
+    "kh_gmm_acc_stats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_int, c_int64_p, c_int32_p, c_int64_p, vp, C.c_int,
+                                   c_double_p, c_double_p, c_double_p]),
+    "kh_gmm_acc_component_posteriors": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, c_int32_p, C.c_int, c_int64_p, c_int32_p,
+                                                  c_float_p, c_int64_p, vp, vp]),
+    "kh_gmm_acc_chunk": (C.c_int, []),
+    "kh_gmm_acc_max_dim": (C.c_int, []),
+    "kh_gmm_acc_set_workspace_limit": (C.c_int, [C.c_size_t]),
+    "kh_gmm_acc_last_timings": (C.c_int, [c_float_p, c_int32_p]),
     "kh_lattice_forward_backward_mpe": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, c_int32_p, C.c_int, C.c_int, c_float_p, c_double_p, c_int32_p]),
     "kh_rescore_lattice": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, vp, C.c_int, c_int32_p, vp]),
     "kh_merge_pair_vector_summing": (C.c_int, [i64, c_int32_p, c_int32_p, c_float_p, i32, c_int32_p, c_int32_p, c_float_p, c_int64_p]),

@@ -1694,6 +1694,147 @@ def write_am_diag_gmm(f, am, binary=True):
                        am["inv_vars"][off[j]:off[j + 1]], binary)
 
 
+# ---------------------------------------------------------------- GMM accumulators (the .acc files between gmm-acc-stats-* and gmm-est)
+# An accumulator is dict(occ [NG], mean_acc [NG, D] | None, var_acc [NG, D] | None  (float64), pdf_offsets [num_pdfs + 1],
+# dim, flags (the augmented GmmFlagsType as Resize stores it: m 1, v 2, w 4, t 8; kGmmAll = 15), total_like, total_frames, transition_accs [num tids + 1] float64 | None).
+def _flags_string(bits):
+    return "".join(c for c, b in (("m", 1), ("v", 2), ("w", 4), ("t", 8)) if bits & b)
+
+
+def write_gmm_accs(f, acc, binary=True, tail=True):
+    """The body of an .acc file: Vector<double>::Write of the transition accumulators (when acc carries them), then
+    AccumAmDiagGmm::Write (gmm/mle-am-diag-gmm.cc:153-166) over AccumDiagGmm::Write (gmm/mle-diag-gmm.cc:77-103): the
+    accumulators are converted to float before writing; <FLAGS> is a GmmFlagsType (uint16: size byte -2).  tail = False
+    leaves out <total_like> / <total_frames>, as the older files the reader tolerates."""
+    off = np.asarray(acc["pdf_offsets"], np.int64)
+    if acc.get("transition_accs") is not None:
+        write_vector(f, np.asarray(acc["transition_accs"], np.float64), binary)
+    write_token(f, binary, "<NUMPDFS>")
+    write_int32(f, binary, len(off) - 1)
+    empty = np.zeros((0, 0), np.float32)
+    for j in range(len(off) - 1):
+        g0, g1 = int(off[j]), int(off[j + 1])
+        write_token(f, binary, "<GMMACCS>")
+        write_token(f, binary, "<VECSIZE>")
+        write_int32(f, binary, int(acc["dim"]))
+        write_token(f, binary, "<NUMCOMPONENTS>")
+        write_int32(f, binary, g1 - g0)
+        write_token(f, binary, "<FLAGS>")
+        f.write(b"\xfe" + struct.pack("<H", int(acc["flags"])) if binary else b"%d " % int(acc["flags"]))
+        write_token(f, binary, "<OCCUPANCY>")
+        write_vector(f, np.asarray(acc["occ"][g0:g1], np.float64).astype(np.float32), binary)
+        write_token(f, binary, "<MEANACCS>")
+        write_matrix(f, empty if acc["mean_acc"] is None else np.asarray(acc["mean_acc"][g0:g1], np.float64).astype(np.float32), binary)
+        write_token(f, binary, "<DIAGVARACCS>")
+        write_matrix(f, empty if acc["var_acc"] is None else np.asarray(acc["var_acc"][g0:g1], np.float64).astype(np.float32), binary)
+        write_token(f, binary, "</GMMACCS>")
+    if tail:
+        write_token(f, binary, "<total_like>")
+        f.write(b"\x08" + struct.pack("<d", float(acc["total_like"])) if binary else (_fmt(acc["total_like"]) + " ").encode())
+        write_token(f, binary, "<total_frames>")
+        f.write(b"\x08" + struct.pack("<d", float(acc["total_frames"])) if binary else (_fmt(acc["total_frames"]) + " ").encode())
+
+
+def add_gmm_accs(into, acc):
+    """into += acc in double, with the checks and messages of Read(..., add = true): AccumAmDiagGmm::Read
+    (mle-am-diag-gmm.cc:131-135), AccumDiagGmm::Read (mle-diag-gmm.cc:46-54), Vector::Read (kaldi-vector.cc)."""
+    a, b = np.diff(np.asarray(into["pdf_offsets"], np.int64)), np.diff(np.asarray(acc["pdf_offsets"], np.int64))
+    if len(a) != len(b):
+        raise ValueError("Adding accumulators but num-pdfs do not match: %d vs. %d" % (len(a), len(b)))
+    bad = np.nonzero(a != b)[0]
+    if len(bad) or int(into["dim"]) != int(acc["dim"]) or int(into["flags"]) != int(acc["flags"]):
+        j = int(bad[0]) if len(bad) else 0
+        raise ValueError("MlEstimatediagGmm::Read, dimension or flags mismatch, %d, %d, %s vs. %d, %d, %d (mixing accs from different models?"
+                         % (a[j], into["dim"], _flags_string(int(into["flags"])), b[j], acc["dim"], acc["flags"]))
+    ta, tb = into.get("transition_accs"), acc.get("transition_accs")
+    if ta is not None and tb is not None:
+        if len(ta) != len(tb):
+            raise ValueError("Vector<Real>::Read, adding but dimensions mismatch %d vs. %d" % (len(ta), len(tb)))
+        ta += tb
+    elif tb is not None:
+        into["transition_accs"] = np.array(tb, np.float64)
+    for k in ("occ", "mean_acc", "var_acc"):
+        if into[k] is not None:
+            into[k] += acc[k]
+    into["total_like"] += acc["total_like"]
+    into["total_frames"] += acc["total_frames"]
+    return into
+
+
+def read_gmm_accs(s, binary=True, add_into=None, transitions=True):
+    """The reader of write_gmm_accs' layout (Vector<double>::Read, AccumAmDiagGmm::Read mle-am-diag-gmm.cc:117-151,
+    AccumDiagGmm::Read mle-diag-gmm.cc:33-75): the floats of the file widened to double.  A file that ends after the last
+    </GMMACCS> has no totals (0).  add_into: an accumulator the values read are added to, as Read(..., add = true) does."""
+    s = _as_stream(s)
+    trans = None
+    if transitions:
+        if binary:
+            trans = read_vector(s, binary).astype(np.float64)
+        else:
+            s.skip_ws()
+            if s.get() != b"[":
+                raise ValueError("Expected \"[\" at the start of a text vector")
+            rows = _read_text_rows(s)
+            trans = np.asarray(rows[0] if rows else [], np.float64)
+    expect_token(s, binary, "<NUMPDFS>")
+    num_pdfs = read_int32(s, binary)
+    if num_pdfs <= 0:
+        raise ValueError("AccumAmDiagGmm::Read: num_pdfs > 0")
+    if add_into is not None and len(add_into["pdf_offsets"]) - 1 != num_pdfs:
+        raise ValueError("Adding accumulators but num-pdfs do not match: %d vs. %d" % (len(add_into["pdf_offsets"]) - 1, num_pdfs))
+    occ, mean, var, off, dims, flagset = [], [], [], [0], set(), set()
+    for _ in range(num_pdfs):
+        expect_token(s, binary, "<GMMACCS>")
+        expect_token(s, binary, "<VECSIZE>")
+        dim = read_int32(s, binary)
+        expect_token(s, binary, "<NUMCOMPONENTS>")
+        n = read_int32(s, binary)
+        expect_token(s, binary, "<FLAGS>")
+        if binary:
+            if s.get() != b"\xfe":
+                raise ValueError("ReadBasicType: did not get expected integer type (GmmFlagsType, -2)")
+            flags = struct.unpack("<H", s.get(2))[0]
+        else:
+            flags = int(_text_word(s))
+        o = np.zeros(n, np.float64)
+        m = np.zeros((n, dim), np.float64) if flags & 1 else None
+        v = np.zeros((n, dim), np.float64) if flags & 2 else None
+        tok = read_token(s, binary)
+        while tok != "</GMMACCS>":
+            if tok == "<OCCUPANCY>":
+                o = read_vector(s, binary).astype(np.float64)
+            elif tok == "<MEANACCS>":
+                x = read_matrix(s, binary).astype(np.float64)
+                m = x if flags & 1 else None
+            elif tok == "<DIAGVARACCS>":
+                x = read_matrix(s, binary).astype(np.float64)
+                v = x if flags & 2 else None
+            else:
+                raise ValueError("Unexpected token '%s' in model file " % tok)
+            tok = read_token(s, binary)
+        if len(o) != n or (m is not None and m.shape != (n, dim)) or (v is not None and v.shape != (n, dim)):
+            raise ValueError("AccumDiagGmm::Read: accumulators do not have the sizes of the header (%d, %d)" % (n, dim))
+        occ.append(o); mean.append(m); var.append(v)
+        off.append(off[-1] + n)
+        dims.add(dim)
+        flagset.add(flags)
+    if len(dims) != 1 or len(flagset) != 1:
+        raise ValueError("AccumAmDiagGmm::Read: the pdfs' accumulators differ in dimension or flags")
+    flags = flagset.pop()
+    like = frames = 0.0
+    if not binary:
+        s.skip_ws()
+    if not s.eof():
+        expect_token(s, binary, "<total_like>")
+        like = read_double(s, binary)
+        expect_token(s, binary, "<total_frames>")
+        frames = read_double(s, binary)
+    acc = dict(occ=np.concatenate(occ), mean_acc=np.concatenate(mean, 0) if flags & 1 else None,
+               var_acc=np.concatenate(var, 0) if flags & 2 else None, pdf_offsets=np.asarray(off, np.int32), dim=dims.pop(),
+               flags=flags, total_like=like, total_frames=frames, transition_accs=trans)
+    return acc if add_into is None else add_gmm_accs(add_into, acc)
+
+
 def read_ivector_extractor(s, binary=True):
     """IvectorExtractor::Read (ivector/ivector-extractor.cc:727-748): dict(w [n x S] or empty, w_vec [n],
     M [n x D x S], Sigma_inv [n x D x D] (full), prior_offset), all float64."""

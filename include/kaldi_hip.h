@@ -1358,6 +1358,49 @@ int kh_gmm_acc_set_workspace_limit(size_t bytes);
  * chunks, workgroups of the accumulation kernel. */
 int kh_gmm_acc_last_timings(float *ms, int32_t *counts);
 
+/* ------------------------------------------------------------------ MLLT statistics (csrc/kh_mllt.hip)
+ * gmm-acc-mllt for a batch of stacked frames: MlltAccs::AccumulateFromPosteriors (transform/mllt.cc:131-160) for every entry,
+ * for given Gaussian posteriors that RandPrune has ALREADY been applied to (kh_gmm_acc_component_posteriors' output, brought
+ * to the host, through kh_rand_prune, and back).  Per (entry, Gaussian) item i with a nonzero posterior p, in float,
+ *     mean[d] = fl32(means_invvars[g, d] / inv_vars[g, d]),  o[d] = fl32(mean[d] - x[row, d]),  w[j] = fl32(inv_vars[g, j] * p)
+ * (the division correctly rounded), and in double, for every j and every packed pair a >= b,
+ *     G[j][a (a + 1) / 2 + b] += w[j] * (o[a] * o[b]),
+ * o and w widened first, so that o[a] * o[b] is exact.  feats, means_invvars, inv_vars, gauss_post: DEVICE; the entry list is
+ * kh_gmm_acc_stats' (HOST) and is checked in the same way before any launch (KH_EINVAL naming the pdf or entry).  HOST output
+ * G [D][Q], Q = D (D + 1) / 2, row j the packed SpMatrix G_j, is SET, not added to; no item: zeros.  beta_ (the double sum
+ * of the surviving posteriors) is the caller's.
+ * The items are taken in entry order then Gaussian order and cut into slices of
+ *     kh_mllt_chunk * max(1, ceil(n / (kh_mllt_chunk * kh_mllt_max_slices)))
+ * items; per slice an fp64 matrix-core GEMM W^T T with both operands made on the fly, the slices' partial sums added in
+ * slice order by a second kernel: the same input gives the same bits, and no setting changes a sum.  The sum order is this
+ * tree's, not the reference's frame-by-frame one.  D = 1 ... kh_mllt_max_dim (64); above: KH_EINVAL before any launch. */
+int kh_mllt_acc_stats(const float *feats, int T, int D, int feat_stride, const float *means_invvars, const float *inv_vars,
+                      const int32_t *pdf_offsets, int num_pdfs, const int64_t *frame_entry_offsets, const int32_t *entry_pdf,
+                      const int64_t *entry_gauss_offsets, const float *gauss_post, double *G);
+/* RandPrune (base/kaldi-math.h:169-175) on post[0 .. n) (HOST) in place and in order; host code, no device.  A value that is
+ * 0 or whose magnitude is >= thresh stays; any other takes one draw u = float((rand() + 1.0) / (RAND_MAX + 2.0)) of the C
+ * library's rand() (under a mutex, as the reference's Rand()) and becomes (post >= 0 ? 1.0 : -1.0) * (u <= q ? thresh : 0.0)
+ * rounded to float - a negative value pruned away is -0.0, as there.  q: the reference writes fabs(post) / prune_thresh
+ * inside namespace kaldi with only <cmath> included; unqualified fabs finds the C library's ::fabs(double), not the float
+ * overload of std::fabs, so the quotient is the DOUBLE division double(|post|) / double(thresh) and u is widened for the
+ * comparison.  That is what this function does.  reseed != 0: srand(seed) first (a process that never seeds draws the
+ * sequence of srand(1)).  thresh < 0: KH_EINVAL; thresh == 0: nothing changes and nothing is drawn. */
+int kh_rand_prune(float *post, int64_t n, float thresh, int reseed, unsigned seed);
+/* The same after positioning the generator: srand(seed), `skip` draws discarded, then RandPrune; *draws: the draws taken
+ * (one per value that is neither 0 nor >= thresh in magnitude).  A process that uses the GPU does not own the generator's
+ * state - the HIP runtime reseeds the C library's generator when it initialises and draws from it at some first uses - so
+ * "never seed and the sequence is the reference's" does not hold there.  A job pruned in several calls passes seed 1 (the
+ * state of a process that never seeded) and the sum of the earlier calls' draws: the posteriors then meet the draws the
+ * reference binary's would, call after call.  The cost is `skip` calls of rand(), some nanoseconds each. */
+int kh_rand_prune_at(float *post, int64_t n, float thresh, unsigned seed, int64_t skip, int64_t *draws);
+int kh_mllt_chunk(void);
+int kh_mllt_max_slices(void);
+int kh_mllt_max_dim(void);
+/* ms[3]: milliseconds of the calling thread's last kh_mllt_acc_stats: the whole call, its host plan (checks, the posteriors'
+ * download, the item list), its two kernels alone (device events).  counts[3]: items, slices, workgroups of the accumulation
+ * kernel (slices x groups of 16 column tiles). */
+int kh_mllt_last_timings(float *ms, int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3468,6 +3468,154 @@ def add_gmm_stats(into, acc):
         raise KhError(str(e))
 
 
+# ---------------------------------------------------------------- MLLT statistics (csrc/kh_mllt.hip)
+# gmm-acc-mllt for stacked frames, over the same entry lists.  An accumulator is dict(beta, G [D, D (D + 1) / 2] float64, dim):
+# row j of G is the packed lower triangle of MlltAccs' G_[j].
+def mllt_acc_stats(am, feats, ent, gauss_post):
+    """MlltAccs::AccumulateFromPosteriors (transform/mllt.cc:131-160) for every entry, for Gaussian posteriors that RandPrune
+    has already been applied to (kh_mllt_acc_stats).  am: AmDiagGmm; feats: 2-D float32 device tensor of the model's
+    dimension, at most mllt_max_dim(); gauss_post: float32 device tensor.  Returns G, float64 host array [D, D (D + 1) / 2]."""
+    T, D, stride = _feat_args(feats)
+    if D != am.dim:
+        raise KhError("MlltAccs::AccumulateFromPosteriors, dimension mismatch %d vs. %d" % (D, am.dim))
+    feo, pdf, goff = _entry_ptrs(ent, T)
+    if gauss_post.dtype != torch.float32 or not gauss_post.is_cuda or gauss_post.numel() != int(goff[-1]):
+        raise KhError("mllt_acc_stats: %d Gaussian posteriors for entries that hold %d" % (gauss_post.numel(), int(goff[-1])))
+    gauss_post = gauss_post.contiguous()
+    off = _host_pdf_offsets(am)
+    G = np.zeros((D, D * (D + 1) // 2), np.float64)
+    ip, lp = capi.c_int32_p, capi.c_int64_p
+    check(lib().kh_mllt_acc_stats(_p(feats), T, D, stride, _p(am.means_invvars), _p(am.inv_vars), off.ctypes.data_as(ip), am.num_pdfs,
+                                  feo.ctypes.data_as(lp), pdf.ctypes.data_as(ip), goff.ctypes.data_as(lp), _p(gauss_post),
+                                  G.ctypes.data_as(capi.c_double_p)))
+    return G
+
+
+def rand_prune(post, thresh, seed=None):
+    """RandPrune (base/kaldi-math.h:169-175) on a host float32 array, in place and in order, with the C library's rand()
+    (kh_rand_prune; no device).  seed: srand(seed) first; None leaves the generator as it is - a process that never seeds
+    draws the reference's sequence.  Returns post."""
+    if not isinstance(post, np.ndarray) or post.dtype != np.float32 or not post.flags.c_contiguous:
+        raise KhError("rand_prune: a contiguous float32 host array is needed")
+    check(lib().kh_rand_prune(post.ctypes.data_as(capi.c_float_p), post.size, float(thresh), 0 if seed is None else 1,
+                              0 if seed is None else int(seed)))
+    return post
+
+
+def rand_prune_at(post, thresh, seed, skip):
+    """rand_prune with the generator put in its place first: srand(seed), `skip` draws discarded (kh_rand_prune_at).  A
+    process that uses the GPU does not own the C library's generator - the HIP runtime reseeds it when it initialises and
+    draws from it at some first uses - so a job pruned in several calls passes seed 1 (the state of a process that never
+    seeded) and the draws of its earlier calls.  Returns the number of draws taken."""
+    if not isinstance(post, np.ndarray) or post.dtype != np.float32 or not post.flags.c_contiguous:
+        raise KhError("rand_prune_at: a contiguous float32 host array is needed")
+    draws = C.c_int64(0)
+    check(lib().kh_rand_prune_at(post.ctypes.data_as(capi.c_float_p), post.size, float(thresh), int(seed), int(skip), C.byref(draws)))
+    return int(draws.value)
+
+
+_rand_prune = rand_prune       # accumulate_mllt_stats takes the reference's option name as a parameter
+
+
+def mllt_chunk():
+    """Items per slice of the MLLT accumulation, times a whole number (kChunk of csrc/kh_mllt.hip)."""
+    return int(lib().kh_mllt_chunk())
+
+
+def mllt_max_slices():
+    return int(lib().kh_mllt_max_slices())
+
+
+def mllt_max_dim():
+    return int(lib().kh_mllt_max_dim())
+
+
+def mllt_last_timings():
+    """The calling thread's last mllt_acc_stats: milliseconds of the call, its host plan and its kernels; items, slices,
+    workgroups."""
+    return _timings(lib().kh_mllt_last_timings, ("call_ms", "plan_ms", "kernels_ms"), ("items", "slices", "workgroups"))
+
+
+def _entry_sums(post, goff):
+    """Per entry the double sum of its float posteriors in Gaussian order (this_beta_ of mllt.cc:143-157: a zero adds
+    nothing), vectorised over the entries: one pass per Gaussian index."""
+    goff = np.asarray(goff, np.int64)
+    sizes = np.diff(goff)
+    s = np.zeros(len(sizes), np.float64)
+    for i in range(int(sizes.max()) if len(sizes) else 0):
+        m = np.nonzero(sizes > i)[0]
+        s[m] += post[goff[m] + i].astype(np.float64)
+    return s
+
+
+def accumulate_mllt_stats(am, feats, pdf_posts, rand_prune=0.25, seed=None, into=None, return_entries=False, segments=None):
+    """MlltAccs::AccumulateFromGmm (mllt.cc:162-170) for every (frame, pdf, weight) of the stacked frames: the posteriors by
+    gmm_acc_component_posteriors, brought to the host, pruned there in entry order then Gaussian order, beta as the double
+    sum over the entries, in order, of each entry's double sum of its surviving posteriors, then the pruned posteriors back
+    on the device and mllt_acc_stats.
+    seed None: the pruning draws from the C library's generator as it stands (the module's rand_prune).  seed s: the job's
+    draws are those of srand(s), and this call's begin where into's ended (rand_prune_at with into["draws"]): 1 gives what a
+    reference binary draws, however the job is cut into calls and whatever else in the process touches the generator - the
+    HIP runtime does.
+    into: a dict this function returned (the dims must agree): G is added to it in double, and beta runs on from its beta
+    entry by entry, as the reference's does from utterance to utterance.  Returns dict(beta, G, dim, draws), draws the
+    job's so far.  return_entries: also the entry list and the entries' scores (host float32): (accumulator, ent, like).
+    segments: row offsets [S + 1] of the call's utterances (0 ... T).  The posteriors, the pruning and the transfers are
+    still one pass, but mllt_acc_stats then runs per segment and the segments' G are added in order, each into the running
+    sum: a sum tree that depends on the utterances alone, so a job gives the same bits however its utterances are grouped
+    into calls (the tool's --batch-frames).  Without segments the call is one accumulation, whose slices depend on where
+    the call begins and ends."""
+    thresh = rand_prune
+    off = _host_pdf_offsets(am)
+    ent = fmllr_entries(pdf_posts, off)
+    before = 0 if into is None else int(into.get("draws", 0))
+    draws = 0
+    if len(ent["pdf"]):
+        post, like = gmm_acc_component_posteriors(am, feats, ent)
+        post, like = np.ascontiguousarray(post.cpu().numpy()), like.cpu().numpy()
+        if seed is None:
+            draws = int(((post != 0) & (np.abs(post) < np.float32(thresh))).sum())      # one draw for each such value
+            _rand_prune(post, thresh)
+        else:
+            draws = rand_prune_at(post, thresh, seed, before)
+        s = _entry_sums(post, ent["goff"])
+        post = torch.from_numpy(post).to(feats.device)
+    else:
+        if float(thresh) < 0:
+            raise KhError("rand_prune: prune threshold %g, must be >= 0" % thresh)
+        post, like, s = torch.zeros(0, dtype=torch.float32, device=feats.device), np.zeros(0, np.float32), np.zeros(0)
+    # beta_ += this_beta_, entry by entry, on from into's: however a job is cut into calls, beta is the same double
+    beta = float(np.cumsum(np.concatenate([[0.0 if into is None else float(into["beta"])], s]))[-1])
+    dim = int(feats.shape[1])
+    acc = into if into is not None else dict(beta=0.0, G=np.zeros((dim, dim * (dim + 1) // 2), np.float64), dim=dim)
+    if int(acc["dim"]) != dim:
+        raise KhError("MlltAccs::Read, summing accs of different size.")         # as add_mllt_stats
+    if segments is None:
+        acc["G"] += mllt_acc_stats(am, feats, ent, post)
+    else:
+        seg = np.asarray(segments, np.int64).reshape(-1)
+        if len(seg) < 1 or seg[0] != 0 or seg[-1] != feats.shape[0] or (np.diff(seg) < 0).any():
+            raise KhError("accumulate_mllt_stats: segments must run from 0 to %d without going backwards" % feats.shape[0])
+        feo, goff = ent["feo"], ent["goff"]
+        for r0, r1 in zip(seg[:-1].tolist(), seg[1:].tolist()):
+            e0, e1 = int(feo[r0]), int(feo[r1])
+            if e1 > e0:
+                g0, g1 = int(goff[e0]), int(goff[e1])
+                sub = dict(feo=feo[r0:r1 + 1] - e0, pdf=ent["pdf"][e0:e1], weight=ent["weight"][e0:e1], goff=goff[e0:e1 + 1] - g0)
+                acc["G"] += mllt_acc_stats(am, feats[r0:r1], sub, post[g0:g1])
+    acc["beta"], acc["draws"] = beta, before + draws
+    return (acc, ent, like) if return_entries else acc
+
+
+def add_mllt_stats(into, acc):
+    """into += acc in double, as MlltAccs::Read with add = true, with its size-mismatch message."""
+    from . import kaldi_io
+    try:
+        return kaldi_io.add_mllt_accs(into, acc)
+    except ValueError as e:
+        raise KhError(str(e))
+
+
 # ---- host posterior / transform algebra of the fMLLR recipes
 def weight_silence_post(tid2phone, silence_phones, silence_scale, post, distribute=False):
     """WeightSilencePost / WeightSilencePostDistributed (hmm/posterior.cc:361-413): tid2phone indexed by transition-id."""

@@ -1835,6 +1835,68 @@ def read_gmm_accs(s, binary=True, add_into=None, transitions=True):
     return acc if add_into is None else add_gmm_accs(add_into, acc)
 
 
+# ---------------------------------------------------------------- MLLT accumulators (the .macc files between gmm-acc-mllt and est-mllt)
+# An accumulator is dict(beta float, G [D, Q] float64 - row j the packed lower triangle of G_j, Q = D (D + 1) / 2 -, dim).
+def _packed_to_full(row, dim):
+    out = np.zeros((dim, dim), np.float64)
+    r, c = np.tril_indices(dim)
+    out[r, c] = row
+    out[c, r] = row
+    return out
+
+
+def write_mllt_accs(f, acc, binary=True):
+    """MlltAccs::Write (transform/mllt.cc:51-63): <MlltAccs>, beta_ (double), dim (int32), <G>, dim SpMatrix<double>,
+    </MlltAccs>; in text a line break after the first token, after <G> and after the last token."""
+    dim = int(acc["dim"])
+    G = np.asarray(acc["G"], np.float64).reshape(dim, dim * (dim + 1) // 2)
+    write_token(f, binary, "<MlltAccs>")
+    if not binary:
+        f.write(b"\n")
+    f.write(b"\x08" + struct.pack("<d", float(acc["beta"])) if binary else (_fmt(acc["beta"]) + " ").encode())
+    write_int32(f, binary, dim)
+    write_token(f, binary, "<G>")
+    if not binary:
+        f.write(b"\n")
+    for j in range(dim):
+        write_sp_matrix(f, _packed_to_full(G[j], dim), binary)
+    write_token(f, binary, "</MlltAccs>")
+    if not binary:
+        f.write(b"\n")
+
+
+def add_mllt_accs(into, acc):
+    """into += acc in double, as MlltAccs::Read with add = true (mllt.cc:34-49), with its message."""
+    if int(into["dim"]) != 0 and int(into["dim"]) != int(acc["dim"]):
+        raise ValueError("MlltAccs::Read, summing accs of different size.")
+    if int(into["dim"]) == 0:
+        into["dim"], into["G"] = int(acc["dim"]), np.zeros_like(np.asarray(acc["G"], np.float64))
+    into["beta"] = float(into["beta"]) + float(acc["beta"])
+    into["G"] += acc["G"]
+    return into
+
+
+def read_mllt_accs(s, binary=True, add_into=None):
+    """MlltAccs::Read (mllt.cc:34-49).  add_into: an accumulator the values read are added to (add = true)."""
+    s = _as_stream(s)
+    expect_token(s, binary, "<MlltAccs>")
+    beta = read_double(s, binary)
+    dim = read_int32(s, binary)
+    if add_into is not None and int(add_into["dim"]) != 0 and dim != int(add_into["dim"]):
+        raise ValueError("MlltAccs::Read, summing accs of different size.")
+    expect_token(s, binary, "<G>")
+    r, c = np.tril_indices(dim)
+    G = np.zeros((dim, dim * (dim + 1) // 2), np.float64)
+    for j in range(dim):
+        M = read_sp_matrix(s, binary)
+        if M.shape[0] != dim:
+            raise ValueError("MlltAccs::Read: G[%d] has %d rows, the accumulator %d" % (j, M.shape[0], dim))
+        G[j] = M[r, c]
+    expect_token(s, binary, "</MlltAccs>")
+    acc = dict(beta=beta, G=G, dim=dim)
+    return acc if add_into is None else add_mllt_accs(add_into, acc)
+
+
 def read_ivector_extractor(s, binary=True):
     """IvectorExtractor::Read (ivector/ivector-extractor.cc:727-748): dict(w [n x S] or empty, w_vec [n],
     M [n x D x S], Sigma_inv [n x D x D] (full), prior_offset), all float64."""

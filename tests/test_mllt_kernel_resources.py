@@ -1,0 +1,40 @@
+"""Compile-only guard (no GPU: hipcc cross-compiles): the kernels of csrc/kh_mllt.hip - MlltAccumulateKernel for 1 ... 4 row
+tiles and MlltReduceKernel - spill no register at the library's own flags, use no scratch and have no dynamic stack.
+MlltAccumulateKernel's static LDS is the figure its header comment derives: the o image of 32 items at a pitch of 65 floats
+and the w image at a pitch of 80 (32 x 65 x 4 + 32 x 80 x 4 = 18560 bytes).  Register counts are printed and recorded in
+DESIGN.md, not asserted."""
+import os
+import re
+import subprocess
+
+from conftest import ROOT, pkg
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def test_mllt_kernel_resources(tmp_path):
+    build = pkg("build")
+    src = os.path.join(ROOT, "old-kaldi-git_amd", "csrc", "kh_mllt.hip")
+    text = open(src).read()
+    p = subprocess.run([HIPCC] + build.flags_for(src) + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", str(tmp_path / "k.o")],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S+)", p.stderr)
+    assert len(re.findall(r"^__global__", text, flags=re.M)) == 2 and len(names) == 5, names
+    acc = [n for n in names if "MlltAccumulateKernel" in n]
+    assert len(acc) == 4 and sum("MlltReduceKernel" in n for n in names) == 1, names
+    get = lambda what: [int(x) for x in re.findall(re.escape(what) + r":\s*(\d+)", p.stderr)]
+    print("kernels", names, "VGPRs", get("VGPRs"), "AGPRs", get("AGPRs"), "SGPRs", get("SGPRs"), "LDS", get("LDS Size [bytes/block]"),
+          "scratch", get("ScratchSize [bytes/lane]"), "occupancy", get("Occupancy [waves/SIMD]"))
+    assert get("VGPRs Spill") == [0] * 5 and get("SGPRs Spill") == [0] * 5
+    assert p.stderr.count("Dynamic Stack: False") == 5
+    assert get("ScratchSize [bytes/lane]") == [0] * 5
+    lds = dict(zip(names, get("LDS Size [bytes/block]")))
+    # the figure of the header comment, and the constants it is made of
+    m = re.search(r"(\d+) x (\d+) x 4 \+ (\d+) x (\d+) x 4 = (\d+) bytes", text)
+    assert m and int(m.group(1)) * int(m.group(2)) * 4 + int(m.group(3)) * int(m.group(4)) * 4 == int(m.group(5)) == 18560
+    assert m.group(1) == m.group(3) and re.search(r"constexpr int kSub = %s;" % m.group(1), text)
+    assert re.search(r"constexpr int kOs = %s;" % m.group(2), text) and re.search(r"constexpr int kWs = %s;" % m.group(4), text)
+    assert [lds[n] for n in acc] == [18560] * 4
+    assert [v for n, v in lds.items() if n not in acc] == [0]
+    assert "atomic" not in text.lower()

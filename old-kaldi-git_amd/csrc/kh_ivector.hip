@@ -264,14 +264,22 @@ struct IvExact {
 // Eigen-decomposition: cyclic Jacobi with the round-robin ("tournament") ordering - n / 2 disjoint rotations per round, all
 // lanes busy - on the full matrix in a scratch slot (device memory, L2-resident; LDS holds the packed statistics).
 constexpr int kEigSlots = 16;
+constexpr int kJacobiPairs = 128;   // rotations of one round: half of the largest dimension solved this way (S <= 256)
+
+// LDS per workgroup.  A launch gets static + dynamic LDS together, 64 KB without an opt-in.  The static share of each
+// kernel is stated here from its __shared__ declarations (tests/test_ivector_kernel_resources.py holds the compiler's
+// figures to these), so that the host can refuse a model that does not fit instead of failing at the launch.
+constexpr size_t kLdsLimit = 64 * 1024;
+constexpr size_t kRedLds = 8 * sizeof(double);                                                          // red[8]
+constexpr size_t kExactLds = 8 + kJacobiPairs * (2 * sizeof(double) + 2 * sizeof(int));                 // s_slot (padded), jc, js, jp, jq
 inline IvExact Exact(const KhIvectorExtractor *x) { return IvExact{x->n_exact, x->eig_scratch, x->eig_locks, kEigSlots}; }
 
 template <int kNW = 4>
 __device__ void IvSolveQuadraticProblem(const double *quad, const double *lin, double *xv, double *rv, double *pv, int S, double *red,
                                         const IvExact &ex) {
   __shared__ int s_slot;
-  __shared__ double jc[128], js[128];
-  __shared__ int jp[128], jq[128];
+  __shared__ double jc[kJacobiPairs], js[kJacobiPairs];
+  __shared__ int jp[kJacobiPairs], jq[kJacobiPairs];
   const int t_id = threadIdx.x, nt = blockDim.x;
   if (t_id == 0) {
     int slot = -1;
@@ -467,7 +475,7 @@ __device__ __forceinline__ void IvGetIvector(const double *quad, const double *l
           if (t_id < S) xv[t_id] = x0[t_id];
           if (t_id == 0 && ex.n_fallback) atomicAdd(ex.n_fallback, 1);
           __syncthreads();
-          if (ex.scratch != nullptr && S <= 256) {   // the reference's exact optimisation (wider models: CG to convergence below)
+          if (ex.scratch != nullptr && S <= 2 * kJacobiPairs) {   // the reference's exact optimisation (wider models: CG to convergence below)
             IvSolveQuadraticProblem<kNW>(quad, lin, xv, rv, pv, S, red, ex);
             break;
           }
@@ -478,6 +486,7 @@ __device__ __forceinline__ void IvGetIvector(const double *quad, const double *l
 }
 
 constexpr int kIvThreads = 256;
+constexpr size_t kStatsStaticLds = kRedLds + kExactLds;   // IvStatsKernel: red + the exact fall-back's
 __global__ void __launch_bounds__(kIvThreads)
 IvStatsKernel(const float *__restrict__ F, int f_stride, const int32_t *__restrict__ utt_off,
               const int32_t *__restrict__ post_idx, const float *__restrict__ post_w, int num_gselect, int D, int S, int qdim,
@@ -711,6 +720,7 @@ IvCountKernel(const int32_t *__restrict__ post_idx, const float *__restrict__ po
 // positions of the groups + the work items of IvLinKernel: a Gaussian's postings in pieces of kLinItem
 // (the postings concentrate on few Gaussians: a workgroup per Gaussian would leave the chip idle)
 constexpr int kLinItem = 512;
+constexpr int kSortChunk = 4096;   // postings per block of IvCountKernel / IvScatterKernel
 __global__ void __launch_bounds__(256) IvScanKernel(const int *__restrict__ count, int I, int *__restrict__ start, int *__restrict__ cursor,
                                                     int32_t *__restrict__ item_g, int32_t *__restrict__ item_b, int *__restrict__ n_items) {
   if (threadIdx.x == 0) {   // I <= 2048: a serial scan is nothing
@@ -745,6 +755,7 @@ IvScatterKernel(const int32_t *__restrict__ post_idx, const float *__restrict__ 
 
 // y[posting] = w * (Sigma_g^-1 M_g)^T f_t; a workgroup = one work item (up to kLinItem postings of one Gaussian)
 constexpr int kLinTile = 32;
+constexpr size_t kLinStaticLds = kLinTile * (sizeof(int32_t) + sizeof(double));   // IvLinKernel: ids, ws
 __global__ void __launch_bounds__(256)
 IvLinKernel(const float *__restrict__ F, int f_stride, const float *__restrict__ post_w, int G, int D, int S,
             const double *__restrict__ SiM, const int *__restrict__ start, const int32_t *__restrict__ item_g,
@@ -784,6 +795,8 @@ IvLinKernel(const float *__restrict__ F, int f_stride, const float *__restrict__
 // one workgroup per utterance: estimation points in order.  (Measured: expanding the quadratic term
 // to the full symmetric matrix — conflict-free columns, 80 KB, one workgroup per CU — gives the same
 // rate as the packed triangle at three workgroups per CU: a solve is a chain of ~35 reductions.)
+constexpr int kWChunk = 16;   // frames per chunk of weights (kWChunk x num_gselect <= 256 floats)
+constexpr size_t kSolveStaticLds = kRedLds + kWChunk * kMaxGselect * sizeof(float) + kExactLds;   // IvSolveKernel: red, s_w, the exact fall-back's
 __global__ void __launch_bounds__(kIvThreads)
 IvSolveKernel(const int32_t *__restrict__ utt_off, const int32_t *__restrict__ point_off, const float *__restrict__ post_w, int G, int S,
               int qdim, const double *__restrict__ Quad, const double *__restrict__ Y, double prior_offset, double max_count,
@@ -796,8 +809,8 @@ IvSolveKernel(const int32_t *__restrict__ utt_off, const int32_t *__restrict__ p
   double *lin = quad + qdim;      // [S]
   double *xv = lin + S, *rv = xv + S, *pv = rv + S, *x0 = pv + S;
   __shared__ double red[8];
-  constexpr int kWChunk = 16, kYU = 10;   // frames per chunk of weights (kWChunk x num_gselect <= 256 floats); rows of Y in flight per lane
-  __shared__ float s_w[kWChunk * 16];
+  constexpr int kYU = 10;   // rows of Y in flight per lane
+  __shared__ float s_w[kWChunk * kMaxGselect];
   // longest utterance first: a workgroup's time is proportional to its utterance's length, and in list
   // order the long ones that start last set the kernel's duration
   const int u = order[blockIdx.x], t_id = threadIdx.x;
@@ -919,6 +932,7 @@ IvSolveKernel(const int32_t *__restrict__ utt_off, const int32_t *__restrict__ p
 // negative weights allowed), items (frame < 0) = GetIvector at estimation point -frame - 1 (:243-251), in the
 // order the reference's loop over t produces them.  The per-frame inputs (lda_ features, pruned UBM posteriors)
 // do not depend on the weights and are computed once per utterance.
+constexpr size_t kStreamStaticLds = kRedLds + kMaxGselect * (sizeof(float) + sizeof(int)) + kExactLds;   // IvStreamKernel: red, s_w, s_g, the exact fall-back's
 __global__ void __launch_bounds__(kIvThreads)
 IvStreamKernel(const int32_t *__restrict__ streams, const int32_t *__restrict__ prog_off, const int32_t *__restrict__ item_frame,
                const float *__restrict__ item_w, const int32_t *__restrict__ utt_off, const float *__restrict__ F, int f_stride,
@@ -931,8 +945,8 @@ IvStreamKernel(const int32_t *__restrict__ streams, const int32_t *__restrict__ 
   double *lin = quad + qdim;      // [S]
   double *xv = lin + S, *rv = xv + S, *pv = rv + S, *x0 = pv + S, *feat = x0 + S, *part = feat + D;   // [S] x 4, [D], [num_gselect][S]
   __shared__ double red[8];
-  __shared__ float s_w[16];
-  __shared__ int s_g[16];
+  __shared__ float s_w[kMaxGselect];
+  __shared__ int s_g[kMaxGselect];
   const int u = streams[blockIdx.x], t_id = threadIdx.x;
   const int b = utt_off[u], e = utt_off[u + 1];
   double *q_u = g_quad + static_cast<size_t>(u) * qdim, *cnt_u = g_cnt + static_cast<size_t>(u) * I;
@@ -1018,6 +1032,16 @@ __global__ void IvStreamDiagKernel(int n, int S, int qdim, const double *__restr
   }
 }
 
+// LDS (static + dynamic) of a workgroup of each kernel that keeps model-sized data there; DynLds = the launch's share
+inline size_t Tri(size_t S) { return S * (S + 1) / 2; }
+inline size_t LinDynLds(size_t D, size_t S) { return sizeof(double) * (D * S + kLinTile * D); }
+inline size_t SolveDynLds(size_t S) { return sizeof(double) * (Tri(S) + 5 * S); }
+inline size_t AccDynLds(size_t D, size_t S, size_t G) { return sizeof(double) * (Tri(S) + 5 * S + D + G * S); }   // IvStatsKernel, IvStreamKernel
+inline size_t LinLds(size_t D, size_t S) { return kLinStaticLds + LinDynLds(D, S); }
+inline size_t SolveLds(size_t S) { return kSolveStaticLds + SolveDynLds(S); }
+inline size_t StatsLds(size_t D, size_t S, size_t G) { return kStatsStaticLds + AccDynLds(D, S, G); }
+inline size_t StreamLds(size_t D, size_t S, size_t G) { return kStreamStaticLds + AccDynLds(D, S, G); }
+
 template <class T>
 T *Upload(const T *h, size_t n) {
   T *d = static_cast<T *>(PoolMalloc(sizeof(T) * (n ? n : 1)));
@@ -1054,16 +1078,19 @@ KhIvectorExtractor *kh_ivector_extractor_create(const KhIvectorConfig *cfg, cons
   }
   {
     // The batched statistics kernels keep a Gaussian's Sigma^-1 M block (IvLinKernel) and an estimation point's packed
-    // quadratic term (IvSolveKernel) in dynamic LDS, 64 KB per workgroup without an opt-in; a model beyond that is refused
-    // HERE, with the limit named, instead of failing at extract time.  The reference has no such limit: the
-    // shapes of online2 recipes (feat-dim 40, iVector-dim 100) need 55 KB / 44 KB.
+    // quadratic term (IvSolveKernel) in dynamic LDS, beside their static arrays: 64 KB per workgroup in all without an
+    // opt-in; a model beyond that is refused HERE, with the limit named, instead of failing at extract time.
+    // The reference has no such limit: the shapes of online2 recipes (feat-dim 40, iVector-dim 100) need 42 KB / 48 KB.
     const size_t D_ = c.feat_dim, S_ = c.ivector_dim;
-    const size_t lin_lds = sizeof(double) * (D_ * S_ + static_cast<size_t>(kLinTile) * D_),
-                 solve_lds = sizeof(double) * (S_ * (S_ + 1) / 2 + 5 * S_);
-    if (lin_lds > 64 * 1024 || solve_lds > 64 * 1024) {
-      SetError("kh_ivector_extractor_create: feat-dim %d x ivector-dim %d needs %zu / %zu bytes of LDS per workgroup in the statistics / "
-               "solve kernels; the limit is 65536 (e.g. feat-dim 40: ivector-dim <= 172; ivector-dim 100: feat-dim <= 62)",
-               c.feat_dim, c.ivector_dim, lin_lds, solve_lds);
+    const size_t lin_lds = LinLds(D_, S_), solve_lds = SolveLds(S_);
+    if (lin_lds > kLdsLimit || solve_lds > kLdsLimit) {
+      size_t max_s = 1, max_d = 1;   // the largest iVector dimension the solve kernel holds; the largest feature dimension beside it
+      while (SolveLds(max_s + 1) <= kLdsLimit) max_s++;
+      const size_t s_at = S_ < max_s ? S_ : max_s;
+      while (LinLds(max_d + 1, s_at) <= kLdsLimit) max_d++;
+      SetError("kh_ivector_extractor_create: feat-dim %d x ivector-dim %d needs %zu / %zu bytes of LDS per workgroup (static + dynamic) "
+               "in the statistics / solve kernels; the limit is %zu (ivector-dim <= %zu at any feat-dim; ivector-dim %zu: feat-dim <= %zu)",
+               c.feat_dim, c.ivector_dim, lin_lds, solve_lds, kLdsLimit, max_s, s_at, max_d);
       return nullptr;
     }
   }
@@ -1205,9 +1232,10 @@ int kh_ivector_extract_adapt(const KhIvectorExtractor *x, const float *feats, in
     hipLaunchKernelGGL(IvPosteriorKernel, dim3(DivUp(rows, 4)), dim3(256), 0, st, d_ll, istride, rows, I, G, c.min_post,
                        c.posterior_scale, d_pi, d_pw);
     // statistics + solves
-    const size_t lin_lds = sizeof(double) * (static_cast<size_t>(D) * S + static_cast<size_t>(kLinTile) * D);
-    if (!c.greedy_most_recent && !adapt && (getenv("KH_IVECTOR_SEQUENTIAL") || lin_lds > 64 * 1024)) {   // the per-utterance accumulation (A/B reference; very wide models)
-      const size_t lds = sizeof(double) * (static_cast<size_t>(x->qdim) + 5 * S + D + static_cast<size_t>(G) * S);
+    // (the per-utterance accumulation is the A/B reference; it keeps a frame's partial sums in LDS beside the solve's
+    // vectors, and a model whose share does not fit there takes the batched path, which create() has checked)
+    if (!c.greedy_most_recent && !adapt && getenv("KH_IVECTOR_SEQUENTIAL") && StatsLds(D, S, G) <= kLdsLimit) {
+      const size_t lds = AccDynLds(D, S, G);
       hipLaunchKernelGGL(IvStatsKernel, dim3(n_utts), dim3(kIvThreads), lds, st, d_F, dstride, d_off, d_pi, d_pw, G, D, S, x->qdim, x->U,
                          x->SiM, c.prior_offset, static_cast<double>(c.max_count), c.ivector_period, c.num_cg_iters, ivectors,
                          ivector_stride, Exact(x));
@@ -1225,7 +1253,7 @@ int kh_ivector_extract_adapt(const KhIvectorExtractor *x, const float *feats, in
       if (hipMemcpyAsync(d_poff, poff.data(), sizeof(int32_t) * (n_utts + 1), hipMemcpyHostToDevice, st) != hipSuccess) rc = KH_EDEVICE;
       // scratch per chunk of utterances: <= 16 GB of Quad (8 qdim B per point) + 16 GB of y (8 G S B per frame) at the default sizes
       const long long kMaxRows = getenv("KH_IVECTOR_MAX_ROWS") ? atoll(getenv("KH_IVECTOR_MAX_ROWS")) : 4000000;
-      const size_t solve_lds = sizeof(double) * (static_cast<size_t>(x->qdim) + 5 * S);
+      const size_t lin_lds = LinDynLds(D, S), solve_lds = SolveDynLds(S);
       for (int u0 = 0; u0 < n_utts && !rc;) {
         int u1 = u0 + 1;
         while (u1 < n_utts && utt_row_offsets_host[u1 + 1] - utt_row_offsets_host[u0] <= kMaxRows) u1++;
@@ -1257,7 +1285,7 @@ int kh_ivector_extract_adapt(const KhIvectorExtractor *x, const float *feats, in
           hipLaunchKernelGGL(IvGemmF64Kernel, dim3(DivUp(x->qdim, kGemmN), DivUp(pts, kGemmM)), dim3(256), 0, st, d_gc, x->U, d_quad, pts,
                              x->qdim, I);
           (void)hipMemsetAsync(d_count, 0, sizeof(int) * I, st);
-          const int sort_grid = std::max(1, std::min<int>(NumCUs() * 4, static_cast<int>((n_post + 4095) / 4096)));
+          const int sort_grid = std::max(1, std::min<int>(NumCUs() * 4, static_cast<int>((n_post + kSortChunk - 1) / kSortChunk)));
           hipLaunchKernelGGL(IvCountKernel, dim3(sort_grid), dim3(256), 0, st, pi_c, pw_c, n_post, I, d_count);
           hipLaunchKernelGGL(IvScanKernel, dim3(1), dim3(256), 0, st, d_count, I, d_start, d_cursor, d_items, d_items + max_items, d_nitems);
           hipLaunchKernelGGL(IvScatterKernel, dim3(sort_grid), dim3(256), 0, st, pi_c, pw_c, n_post, I, d_cursor, d_sorted);
@@ -1330,7 +1358,14 @@ KhIvectorStreams *kh_ivector_streams_create(const KhIvectorExtractor *x, const f
     SetError("kh_ivector_streams_create: --use-most-recent-ivector / --greedy-ivector-extractor are not supported with frame weights");
     return nullptr;
   }
-  if (c.num_gselect > 16) { SetError("kh_ivector_streams_create: num_gselect %d > 16", c.num_gselect); return nullptr; }
+  if (c.num_gselect > kMaxGselect) { SetError("kh_ivector_streams_create: num_gselect %d > %d", c.num_gselect, kMaxGselect); return nullptr; }
+  if (StreamLds(c.feat_dim, c.ivector_dim, c.num_gselect) > kLdsLimit) {
+    // the streams kernel keeps a frame's feature row and per-posting partial sums in LDS beside what the solve needs
+    SetError("kh_ivector_streams_create: feat-dim %d, ivector-dim %d, num-gselect %d need %zu bytes of LDS per workgroup (static + dynamic) "
+             "in the streams kernel; the limit is %zu", c.feat_dim, c.ivector_dim, c.num_gselect,
+             StreamLds(c.feat_dim, c.ivector_dim, c.num_gselect), kLdsLimit);
+    return nullptr;
+  }
   for (int u = 0; u < n_utts; u++)
     if (utt_row_offsets_host[u + 1] <= utt_row_offsets_host[u]) { SetError("kh_ivector_streams_create: empty utterance %d", u); return nullptr; }
   const int rows = utt_row_offsets_host[n_utts];
@@ -1508,7 +1543,7 @@ int kh_ivector_streams_get_frames(KhIvectorStreams *h, int n, const int32_t *str
   float *d_iw = Upload(item_w.data(), item_w.size());
   if (!d_ids || !d_poff || !d_if || !d_iw) { PoolFree(d_ids); PoolFree(d_poff); PoolFree(d_if); PoolFree(d_iw); return KH_ENOMEM; }
   const int D = c.feat_dim, S = c.ivector_dim, G = c.num_gselect;
-  const size_t lds = sizeof(double) * (static_cast<size_t>(h->x->qdim) + 5 * S + D + static_cast<size_t>(G) * S);
+  const size_t lds = AccDynLds(D, S, G);
   hipLaunchKernelGGL(IvStreamKernel, dim3(na), dim3(kIvThreads), lds, st, d_ids, d_poff, d_if, d_iw, h->d_off, h->d_F, h->dstride, h->d_pi,
                      h->d_pu, G, D, S, h->x->qdim, c.num_gauss, h->x->U, h->x->SiM, static_cast<double>(c.prior_offset),
                      static_cast<double>(c.max_count), c.posterior_scale, c.ivector_period, c.num_cg_iters, h->d_quad, h->d_lin, h->d_xv,

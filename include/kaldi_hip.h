@@ -688,6 +688,13 @@ int kh_lattice_batch_forward_backward_dev(KhLatticeBatch *batch, float *arc_post
 int kh_lattice_batch_rescore(KhLatticeBatch *batch, const float *loglikes, int ll_stride, const int32_t *ll_row_offsets,
                              const int32_t *tid2pdf, float *arc_acoustic_out);
 int kh_lattice_last_timings(float *ms4);
+/* Which forms of the lattice kernels the last lattice call of this thread ran (the sizing: csrc/kh_lattice_plan.h), 12 words:
+ * [0] CUs of the device; the preparation: [1] 1 = dataflow (PrepKernelDF), 0 = dependency levels (PrepKernel), [2] workgroups
+ * planned per CU, [3] slots of the state-time window, [4] states whose counters stay in LDS ([2], [3]: 0 for the level
+ * preparation), [5] lattices of more states than [4] (their counters are in device memory); the forward-backward sweep:
+ * [6] 1 = dataflow, 0 = by level, -1 = the call ran none, [7] workgroups planned per CU, [8] arcs staged per wave, [9] slots
+ * of the value window, [10] lattices of more states than [9] (tagged window) ([7]-[10]: 0 unless [6] = 1); [11] 0. */
+int kh_lattice_last_plan(int32_t *out12);
 
 /* ComputeLatticeAlphasAndBetas (lat/lattice-functions.cc:412-463) for a batch (same CSR
  * layout as above): alpha / beta per state (log-semiring, or the tropical one when

@@ -1216,6 +1216,18 @@ def lattice_state_times(L):
     return times
 
 
+def lattice_state_times_batch(lats):
+    """LatticeStateTimes of a batch on the device (kh_lattice_state_times: the preparation kernel alone, no costs uploaded):
+    per lattice dict(state_times, max_time); -1 for a state no path from state 0 reaches."""
+    n, soff, aoff, il, ns, _, _, fin = _cat_lattices(lats)
+    times, max_times = np.empty(int(soff[-1]), np.int32), np.empty(n, np.int32)
+    ip = capi.c_int32_p
+    check(lib().kh_lattice_state_times(n, soff.ctypes.data_as(ip), aoff.ctypes.data_as(capi.c_int64_p), il.ctypes.data_as(ip),
+                                       ns.ctypes.data_as(ip), fin.ctypes.data_as(capi.c_float_p), times.ctypes.data_as(ip),
+                                       max_times.ctypes.data_as(ip)))
+    return [dict(state_times=times[soff[i]:soff[i + 1]].copy(), max_time=int(max_times[i])) for i in range(n)]
+
+
 class LatticeBatch:
     """A batch of top-sorted lattices kept on the device (kh_lattice_batch_*): uploaded and prepared once; forward-backward,
     rescoring with a new score matrix and the forward-backward after it run from there (what
@@ -1277,6 +1289,20 @@ def lattice_last_timings():
     ms = (C.c_float * 4)()
     check(lib().kh_lattice_last_timings(ms))
     return dict(upload_ms=ms[0], prep_ms=ms[1], sweeps_ms=ms[2], download_ms=ms[3])
+
+
+_LATTICE_PLAN_FIELDS = ("cus", "prep_dataflow", "prep_per_cu", "prep_win", "prep_lds_states", "n_prep_off_lds",
+                        "sweep_dataflow", "sweep_per_cu", "sweep_stage", "sweep_win", "n_tagged")
+
+
+def lattice_last_plan():
+    """Which forms of the lattice kernels the last lattice call of this thread ran (kh_lattice_last_plan; the sizing is
+    csrc/kh_lattice_plan.h): the preparation (dataflow or levels, workgroups per CU, state-time window, states whose counters
+    stay in LDS, lattices above that) and the forward-backward sweep (1 dataflow / 0 levels / -1 none, workgroups per CU,
+    staged arcs per wave, window slots, lattices in the tagged form)."""
+    out = np.zeros(12, np.int32)
+    check(lib().kh_lattice_last_plan(out.ctypes.data_as(capi.c_int32_p)))
+    return {k: int(v) for k, v in zip(_LATTICE_PLAN_FIELDS, out)}
 
 
 # ---------------------------------------------------------------- best paths over score points (csrc/kh_latbest.hip)

@@ -173,6 +173,7 @@ SIGNATURES = {
     "kh_lattice_batch_forward_backward_dev": (C.c_int, [vp, vp, c_double_p, c_double_p]),
     "kh_lattice_batch_rescore": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "kh_lattice_last_timings": (C.c_int, [C.POINTER(C.c_float)]),
+    "kh_lattice_last_plan": (C.c_int, [c_int32_p]),
     "kh_decoder_set_reference_order": (C.c_int, [vp, C.c_int]),
     "kh_decoder_get_search_counters": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64)]),
     "kh_decoder_get_stats": (C.c_int, [vp, C.c_int, C.POINTER(KhDecodeStats)]),

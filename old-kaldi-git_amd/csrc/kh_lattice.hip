@@ -5,12 +5,16 @@
 //
 // The reference sweeps the states sequentially (alpha forward, beta backward,
 // LogAdd in double).  Here each lattice gets one workgroup; states are grouped
-// into dependency levels (longest distance from the start state, computed on
-// the host in O(arcs) while the CSR is validated), a level is processed by all
-// threads at once, and each state accumulates its incoming (alpha) / outgoing
-// (beta) arcs in ascending arc order — the same order of LogAdd operands as the
-// reference's sequential sweep, so alpha/beta differ from it only through the
-// device's exp/log1p.  Arc posteriors are written per arc; the caller merges
+// into dependency levels (longest distance from a state without incoming arcs,
+// computed on the device by PrepKernel while the CSR is validated; the host only
+// uploads the caller's arrays), a level is processed by all threads at once, and
+// each state accumulates its incoming (alpha) / outgoing (beta) arcs in ascending
+// arc order — the same order of LogAdd operands as the reference's sequential
+// sweep, so alpha/beta differ from it only through the device's exp/log1p.
+// LatticeForwardBackward itself runs without levels where it can (PrepKernelDF,
+// ForwardBackwardDFKernel below: the states in index order, operands from an LDS
+// window); which form runs is sized in kh_lattice_plan.h and reported by
+// kh_lattice_last_plan.  Arc posteriors are written per arc; the caller merges
 // them per (frame, transition-id) as MergePairVectorSumming does (:351-352).
 #include <algorithm>
 #include <atomic>
@@ -28,6 +32,7 @@
 #include <type_traits>
 
 #include "kh_common.h"
+#include "kh_lattice_plan.h"
 #include "kh_logadd.h"
 
 using namespace kh;
@@ -35,6 +40,7 @@ using namespace kh;
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kh_latplan::kThreads, "kh_lattice_plan.h sizes the LDS of workgroups of kThreads");
 
 struct LatDesc {
   int32_t state_b, n_states;   // range in the concatenated state arrays
@@ -627,7 +633,7 @@ __device__ __forceinline__ void SortIncomingLists(const int64_t *__restrict__ in
   }
 }
 
-constexpr int kPrepLdsStates = 5120;   // 60 KB of LDS for the three work arrays
+constexpr int kPrepLdsStates = kh_latplan::kLevelPrepLdsStates;   // 60 KB of LDS for the three work arrays
 __global__ void __launch_bounds__(kThreads)
 PrepKernel(const int32_t *__restrict__ lat_off, const int64_t *__restrict__ arc_off, const int32_t *__restrict__ il,
            const int32_t *__restrict__ next, const float *__restrict__ fin, LatDesc *__restrict__ descs,
@@ -757,6 +763,8 @@ PrepKernel(const int32_t *__restrict__ lat_off, const int64_t *__restrict__ arc_
 
 constexpr int kWin = 4096;   // states whose value the dataflow sweeps keep in their LDS window
 static_assert((kWin / 64) % (kThreads / 64) == 0, "a window slot is rewritten by the wave that wrote it");
+static_assert(kh_latplan::SameWaveRewrites(kh_latplan::kPrepWinLarge) && kh_latplan::SameWaveRewrites(kh_latplan::kPrepWinSmall) &&
+              kh_latplan::SameWaveRewrites(kh_latplan::kWinMin / 2), "... and so for every window the plan can choose");
 // KH_LATTICE_PROFILE=1: shader-clock stamps of thread 0 of every workgroup (kProf instantiations; [16] words per lattice)
 constexpr int kLatProf = 16;
 #define LAT_STAMP(k) do { if (kProf && threadIdx.x == 0) { const long long now_ = clock64(); prof[blockIdx.x * kLatProf + (k)] += now_ - t_prev_; t_prev_ = now_; } } while (0)
@@ -858,7 +866,7 @@ PrepKernelDF(const int32_t *__restrict__ lat_off, const int64_t *__restrict__ ar
   // sequential sweep), so every list is sorted by arc index - in the block's LDS staging area (the block's lists are
   // contiguous: coalesced loads, a lane sorts its own state's few entries at LDS latency, coalesced stores; one thread per
   // state sorting in device memory took 3.7 M of the 6.4 M cycles of a 16 k-state lattice's preparation).
-  constexpr int kTStage = 384;
+  constexpr int kTStage = kh_latplan::kStageLarge;
   __shared__ int st_src[kThreads / 64][kTStage];
   __shared__ int st_arc[kThreads / 64][kTStage];   // arc index - the lattice's first arc
   __shared__ int st_seg[kThreads / 64][kTStage];   // the entry's list: first entry | length << 16
@@ -1303,6 +1311,13 @@ struct LatTimer {
 };
 static thread_local LatTimer g_lat_timer;
 
+// Which forms the last lattice call of this thread ran (kh_lattice_last_plan; the words: kh_lattice_plan.h).  A batch keeps
+// the preparation's half (LatBatch::plan); a sweep on it reports both halves.
+struct LatPlanRecord {
+  int32_t v[kh_latplan::kRecWords] = {0, 0, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0};
+};
+static thread_local LatPlanRecord g_lat_plan;
+
 // KH_LATTICE_PROFILE=1: the kProf instantiations of the dataflow kernels; prints where thread 0 / wave 0 of the workgroups
 // spent their shader cycles (means over the lattices of the call) to stderr.
 static bool LatProfile() {
@@ -1350,6 +1365,7 @@ struct LatBatch {
   DevArr<float> d_g, d_a, d_fin;
 
   bool has_levels = true;   // dependency levels built (the MPE / alpha-beta / discriminative kernels sweep by level)
+  LatPlanRecord plan;       // how Build sized the preparation (no sweep yet)
   int Build(int n, const int32_t *lat_state_offsets, const int64_t *arc_offsets, const int32_t *arc_ilabel,
             const int32_t *arc_nextstate, const float *arc_graph, const float *arc_acoustic,
             const float *state_final, hipStream_t st, bool want_levels = true) {
@@ -1378,6 +1394,13 @@ struct LatBatch {
     if (arc_acoustic) UP(d_a, arc_acoustic, A, float);
 #undef UP
     g_lat_timer.Mark(1, st);
+    int max_ns = 1;
+    for (int l = 0; l < n_lats; l++) max_ns = std::max(max_ns, lat_state_offsets[l + 1] - lat_state_offsets[l]);
+    const int cus = std::max(1, NumCUs());
+    plan = LatPlanRecord();
+    plan.v[kh_latplan::kRecCus] = cus;
+    plan.v[kh_latplan::kRecPrepDataflow] = want_levels ? 0 : 1;
+    plan.v[kh_latplan::kRecPrepLdsStates] = kPrepLdsStates;
     if (want_levels)
       hipLaunchKernelGGL(PrepKernel, dim3(n_lats), dim3(kThreads), 0, st, d_lat_off.p, d_arc_off.p, d_ilabel.p, d_next.p,
                          d_fin.p, d_descs.p, d_times.p, d_level_off.p, d_level_states.p, d_in_off.p, d_in_arc.p,
@@ -1385,14 +1408,12 @@ struct LatBatch {
     else {
       // dynamic LDS: the state-time window + the per-state counters of the batch's largest lattice, as far as the workgroups
       // that share a CU leave room (larger lattices count in device memory)
-      int max_ns = 1;
-      for (int l = 0; l < n_lats; l++) max_ns = std::max(max_ns, lat_state_offsets[l + 1] - lat_state_offsets[l]);
-      const int cus = std::max(1, NumCUs());
-      const int per_cu = std::min(4, (n_lats + cus - 1) / cus);
-      const int budget = (160 * 1024) / per_cu - 21 * 1024;   // (staging + the static words)
-      const int win = per_cu <= 2 ? 4096 : 1024;
-      const int lds_states = std::max(0, std::min(max_ns, (budget - win * 8) / 4));
-      const size_t dyn = static_cast<size_t>(win) * 8 + static_cast<size_t>(lds_states) * 4;
+      const kh_latplan::PrepPlan pp = kh_latplan::PlanPrep(n_lats, max_ns, cus);
+      const int per_cu = pp.per_cu, win = pp.win, lds_states = pp.lds_states;
+      const size_t dyn = pp.dyn_bytes;
+      plan.v[kh_latplan::kRecPrepPerCu] = per_cu;
+      plan.v[kh_latplan::kRecPrepWin] = win;
+      plan.v[kh_latplan::kRecPrepLdsStates] = lds_states;
       DevArr<long long> d_prof;
       const bool prof = LatProfile();
       if (prof) {
@@ -1420,6 +1441,9 @@ struct LatBatch {
         LatProfilePrint("prep", d_prof, n_lats, st);
       }
     }
+    for (int l = 0; l < n_lats; l++)
+      plan.v[kh_latplan::kRecPrepOffLds] += lat_state_offsets[l + 1] - lat_state_offsets[l] > plan.v[kh_latplan::kRecPrepLdsStates] ? 1 : 0;
+    g_lat_plan = plan;
     KH_LAUNCH_CHECK();
     descs.resize(n_lats);
     std::vector<int32_t> h_err(4 * static_cast<size_t>(n_lats));
@@ -1458,13 +1482,17 @@ static int LaunchForwardBackwardDF(const LatBatch &B, double *alpha, double *bet
   int max_ns = 1;
   for (const LatDesc &d : B.descs) max_ns = std::max(max_ns, d.n_states);
   const int cus = std::max(1, NumCUs());
-  const int per_cu = std::min(4, (n_lats + cus - 1) / cus);   // (more than four resident workgroups per CU: the window gets too small)
-  const bool small_stage = per_cu > 2;
-  const int stage_bytes = (small_stage ? 192 : 384) * 16 * (kThreads / 64) + 256;
-  int win = 512;
-  while (win < 16384 && win < max_ns && (2 * win) * 8 + stage_bytes <= (160 * 1024) / per_cu) win *= 2;
-  if (const char *e = getenv("KH_LATTICE_WIN")) { const int v = atoi(e); if (v >= 512 && v <= 16384 && (v & (v - 1)) == 0) win = v; }
-  const size_t dyn = static_cast<size_t>(win) * sizeof(double);
+  const char *win_env = getenv("KH_LATTICE_WIN");
+  const kh_latplan::SweepPlan sp = kh_latplan::PlanSweep(n_lats, max_ns, cus, win_env ? atoi(win_env) : 0);
+  const int per_cu = sp.per_cu, win = sp.win;
+  const bool small_stage = sp.stage == kh_latplan::kStageSmall;
+  const size_t dyn = sp.dyn_bytes;
+  g_lat_plan = B.plan;
+  g_lat_plan.v[kh_latplan::kRecSweepDataflow] = 1;
+  g_lat_plan.v[kh_latplan::kRecSweepPerCu] = per_cu;
+  g_lat_plan.v[kh_latplan::kRecSweepStage] = sp.stage;
+  g_lat_plan.v[kh_latplan::kRecSweepWin] = win;
+  for (const LatDesc &d : B.descs) g_lat_plan.v[kh_latplan::kRecTagged] += d.n_states > win ? 1 : 0;
   DevArr<long long> d_prof;
   const bool prof = LatProfile();
   if (prof) {
@@ -1484,8 +1512,8 @@ static int LaunchForwardBackwardDF(const LatBatch &B, double *alpha, double *bet
                        B.d_arc_off.p, B.d_next.p, B.d_g.p, B.d_a.p, B.d_fin.p, B.d_in_off.p, B.d_in_arc.p, B.d_in_src.p,     \
                        B.d_final_list.p, d_alpha.p, d_beta.p, d_post.p, d_tot.p, d_ac.p, min_log_diff, d_prof.p, win);       \
   } while (0)
-  if (prof) { if (small_stage) KH_FB_LAUNCH(true, 192); else KH_FB_LAUNCH(true, 384); }
-  else { if (small_stage) KH_FB_LAUNCH(false, 192); else KH_FB_LAUNCH(false, 384); }
+  if (prof) { if (small_stage) KH_FB_LAUNCH(true, kh_latplan::kStageSmall); else KH_FB_LAUNCH(true, kh_latplan::kStageLarge); }
+  else { if (small_stage) KH_FB_LAUNCH(false, kh_latplan::kStageSmall); else KH_FB_LAUNCH(false, kh_latplan::kStageLarge); }
 #undef KH_FB_LAUNCH
   if (prof) {
     KH_LAUNCH_CHECK();
@@ -1510,13 +1538,16 @@ static int RunForwardBackward(const LatBatch &B, float *arc_post, double *tot_li
   struct { float *p; } d_post{post_dev ? post_dev : d_post_own.p};
   const double min_log_diff = log(DBL_EPSILON);  // kMinLogDiffDouble kaldi-math.h:120
   g_lat_timer.Mark(2, st);
-  if (B.has_levels && !getenv("KH_LATTICE_DATAFLOW"))
+  if (B.has_levels && !getenv("KH_LATTICE_DATAFLOW")) {
+    g_lat_plan = B.plan;
+    g_lat_plan.v[kh_latplan::kRecSweepDataflow] = 0;
     hipLaunchKernelGGL(ForwardBackwardKernel, dim3(n_lats), dim3(kThreads), 0, st, B.d_descs.p,
                        B.d_arc_off.p, B.d_next.p, B.d_g.p, B.d_a.p, B.d_fin.p, B.d_level_off.p, B.d_level_states.p,
                        B.d_in_off.p, B.d_in_arc.p, B.d_in_src.p, B.d_final_list.p, d_alpha.p, d_beta.p,
                        d_post.p, d_tot.p, d_ac.p, min_log_diff);
-  else if (int rc_df = LaunchForwardBackwardDF(B, d_alpha.p, d_beta.p, d_post.p, d_tot.p, d_ac.p, min_log_diff, st))
+  } else if (int rc_df = LaunchForwardBackwardDF(B, d_alpha.p, d_beta.p, d_post.p, d_tot.p, d_ac.p, min_log_diff, st)) {
     return rc_df;
+  }
   KH_LAUNCH_CHECK();
   g_lat_timer.Mark(3, st);
   if (arc_post && !post_dev)
@@ -1528,6 +1559,12 @@ static int RunForwardBackward(const LatBatch &B, float *arc_post, double *tot_li
   g_lat_timer.Mark(4, st);
   KH_HIP(hipStreamSynchronize(st));
   g_lat_timer.Finish();
+  return KH_OK;
+}
+
+extern "C" int kh_lattice_last_plan(int32_t *out) {
+  KH_CHECK_ARG(out);
+  for (int i = 0; i < kh_latplan::kRecWords; i++) out[i] = g_lat_plan.v[i];
   return KH_OK;
 }
 
@@ -2302,6 +2339,8 @@ int DiscBegin(KhDiscCall &C,
                        d_posteriors.stride, d_pri.p, acoustic_scale, d_num.p);
     if (d_alpha.Alloc(B.total_states) || d_beta.Alloc(B.total_states)) return KH_ENOMEM;
     if (B.has_levels) {
+      g_lat_plan = B.plan;
+      g_lat_plan.v[kh_latplan::kRecSweepDataflow] = 0;
       hipLaunchKernelGGL(ForwardBackwardKernel, dim3(n_lats), dim3(kThreads), 0, ts, B.d_descs.p, B.d_arc_off.p, B.d_next.p,
                          B.d_g.p, B.d_a.p, B.d_fin.p, B.d_level_off.p, B.d_level_states.p, B.d_in_off.p, B.d_in_arc.p, B.d_in_src.p,
                          B.d_final_list.p, d_alpha.p, d_beta.p, d_post.p, d_tot.p, d_ac.p, log(DBL_EPSILON));

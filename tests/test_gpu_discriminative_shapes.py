@@ -250,12 +250,71 @@ def run_case(api, name, criterion, drop, sliced=False):
     if criterion == "mmi":   # where the posteriors are 0 nothing came out (dropped zero entries; 1 - 1 at frame 0)
         cells = np.concatenate([shape["zero_cells"], shape["one_cells"]])
         assert not deriv[cells[:, 0], cells[:, 1]].any() and not want[cells[:, 0], cells[:, 1]].any()
+    return got
+
+
+MID_CASES = [("mmi", False), ("mmi", True), ("smbr", False)]
+_mid_default = {}
+
+
+def mid_default(api, criterion, drop):
+    """The `mid` shape's checked result at the default switches (once per case; call before a switch is set)."""
+    if (criterion, drop) not in _mid_default:
+        got = run_case(api, "mid", criterion, drop)
+        _mid_default[criterion, drop] = (got, api.lattice_last_plan())
+    return _mid_default[criterion, drop]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("criterion,drop", [("mmi", False), ("mmi", True), ("smbr", False)])
+@pytest.mark.parametrize("criterion,drop", MID_CASES)
 def test_mid_shape(api, criterion, drop):
-    run_case(api, "mid", criterion, drop)
+    got, plan = mid_default(api, criterion, drop)
+    # MMI: dataflow preparation and sweep; sMBR: the level preparation, AlphaBetaKernel + MpeKernel (no forward-backward sweep)
+    want = (1, 1) if criterion == "mmi" else (0, -1)
+    assert (plan["prep_dataflow"], plan["sweep_dataflow"]) == want, plan
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("switch", ["KH_LATTICE_LEVELS", "KH_LATTICE_ONE_STREAM"])
+@pytest.mark.parametrize("criterion,drop", MID_CASES)
+def test_mid_shape_under_a_switch(api, monkeypatch, switch, criterion, drop):
+    """KH_LATTICE_LEVELS=1: MMI's forward-backward runs ForwardBackwardKernel on a level-prepared batch; KH_LATTICE_ONE_STREAM=1:
+    the steps beside the forward pass run on the library's stream.  Either way the checks of run_case hold and the derivative
+    and the statistics EQUAL the default run's: the sweeps fold the same operands in the same order, and the radix sort behind
+    them is stable."""
+    import torch
+    base, _ = mid_default(api, criterion, drop)
+    monkeypatch.setenv(switch, "1")
+    got = run_case(api, "mid", criterion, drop)
+    plan = api.lattice_last_plan()
+    if switch == "KH_LATTICE_LEVELS":
+        assert (plan["prep_dataflow"], plan["sweep_dataflow"]) == ((0, 0) if criterion == "mmi" else (0, -1)), plan
+    else:
+        assert (plan["prep_dataflow"], plan["sweep_dataflow"]) == ((1, 1) if criterion == "mmi" else (0, -1)), plan
+    assert torch.equal(got["deriv"], base["deriv"])
+    assert got["stats"] == base["stats"], (got["stats"], base["stats"])
+    assert got["objf"] == base["objf"] and got["weight"] == base["weight"]
+
+
+@pytest.mark.gpu
+def test_begin_without_a_second_stream_is_refused(api, monkeypatch):
+    """KH_LATTICE_ONE_STREAM=1 leaves nothing for an overlapped call to run on: begin=True raises, and the next plain call
+    is untouched."""
+    import torch
+    shape = make_shape("mid")
+    out = torch.from_numpy(posteriors_of(shape, "mmi")).cuda()
+    egs = [dict(e, feats=torch.zeros((len(e["num_ali"]), 1))) for e in shape["egs"]]
+    call = lambda **kw: api.discriminative_lattice_computations(
+        PreparedOutput(out, shape["row_off"].astype(np.int32)), shape["priors"], shape["tid2pdf"], egs, criterion="mmi", acoustic_scale=0.1,
+        drop_frames=False, tid2phone=shape["tid2phone"], silence_phones=SIL, **kw)
+    base, _ = mid_default(api, "mmi", False)
+    monkeypatch.setenv("KH_LATTICE_ONE_STREAM", "1")
+    with pytest.raises(api.KhError, match="no second stream"):
+        call(begin=True)
+    monkeypatch.delenv("KH_LATTICE_ONE_STREAM")
+    got = call()
+    torch.cuda.synchronize()
+    assert torch.equal(got["deriv"], base["deriv"]) and got["stats"] == base["stats"]
 
 
 @pytest.mark.gpu

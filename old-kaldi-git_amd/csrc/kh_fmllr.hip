@@ -10,12 +10,8 @@
 //                                   (:193-273), ...Diagonal (:275-348), ...Offset (:350-378), FmllrAuxFuncDiagGmm (:481-508);
 //                                   host C++ in double (csrc/kh_fmllr_update.h), threads over speakers, no device
 //
-// A1, one wave per (frame, pdf) entry.  The per-Gaussian scores are kh_gmm.hip's k-ordered fmaf chains
-// (ll = (g + a1) + (-0.5f * a2)), bit-identical to GmmLoglikesKernel.  Then in float: max; e = EXP(fl32(f - max)); the sum
-// of e in Gaussian order; posterior = (e * fl32(1.0 / sum)) * weight; like = max + LOG(sum).  EXP and LOG are libm's
-// expf / logf (the device library's, 1 ulp each), NOT kh_gmm.hip's ExpTerm / LogOfSum: ApplySoftMax has no cutoff, so the
-// exp2 form's argument rounding |f - max| * 2^-24 is not bounded, and the transcendental share of this kernel is one expf
-// per D fmaf pairs.
+// A1, one wave per (frame, pdf) entry: ComponentPosteriorsKernel<false> of kh_gmmstats.h, whose header states the arithmetic
+// (EXP and LOG are the device library's expf / logf here).
 //
 // A2, one 64-lane workgroup per merged frame, lane = dimension: a[d] = fmaf(post, means_invvars[g][d], a[d]) and b[d] with
 // inv_vars, over the merged frame's entries in order and each entry's Gaussians in order; count (double) adds each entry's
@@ -42,7 +38,6 @@
 // The plain v_fma_f64 form of this kernel was not built; on this part the two peak rates are equal, the MFMA form needs two
 // LDS reads per 1024 multiply-adds where the vector form needs operands in registers per lane.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <string>
 #include <thread>
@@ -50,6 +45,7 @@
 
 #include "kh_common.h"
 #include "kh_fmllr_update.h"
+#include "kh_gmmstats.h"
 
 using namespace kh;
 
@@ -57,86 +53,6 @@ namespace {
 
 thread_local float g_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // A1, A2, B, C of this thread's last calls; B's kernels (events); B's groups
 thread_local size_t g_ws_limit = 0;   // kh_fmllr_set_workspace_limit
-
-struct Clock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  float Ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
-// Device buffers of one call, returned to the pool on every exit.
-struct Scratch {
-  std::vector<void *> ptrs;
-  template <typename T> T *Get(size_t n) {
-    void *p = PoolMalloc(sizeof(T) * std::max<size_t>(n, 1));
-    if (p) ptrs.push_back(p);
-    return static_cast<T *>(p);
-  }
-  template <typename T> T *Upload(const T *host, size_t n) {
-    T *p = Get<T>(n);
-    if (p && n && hipMemcpyAsync(p, host, sizeof(T) * n, hipMemcpyHostToDevice, Stream()) != hipSuccess) return nullptr;
-    return p;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(Stream());
-    for (void *p : ptrs) PoolFree(p);
-  }
-};
-
-constexpr int kPostWaves = 4;
-
-__device__ __forceinline__ float ReadLaneF(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// A1.  post is read back only by the lane that wrote the element.
-__global__ void __launch_bounds__(64 * kPostWaves)
-ComponentPosteriorsKernel(const float *__restrict__ feats, int feat_stride, int D, const float *__restrict__ gconsts,
-                          const float *__restrict__ mi, const float *__restrict__ iv, const int32_t *__restrict__ pdf_offsets,
-                          const int32_t *__restrict__ entry_row, const int32_t *__restrict__ entry_pdf,
-                          const float *__restrict__ entry_weight, const int64_t *__restrict__ entry_goff, long long E,
-                          float *post, float *__restrict__ like) {
-  const int lane = threadIdx.x & 63;
-  for (long long e0 = static_cast<long long>(blockIdx.x) * kPostWaves + (threadIdx.x >> 6); e0 < E;
-       e0 += static_cast<long long>(gridDim.x) * kPostWaves) {
-    const int ei = __builtin_amdgcn_readfirstlane(static_cast<int>(e0));   // E < 2^31, checked by the host
-    const int row = __builtin_amdgcn_readfirstlane(entry_row[ei]);
-    const int pdf = __builtin_amdgcn_readfirstlane(entry_pdf[ei]);
-    const int m0 = __builtin_amdgcn_readfirstlane(pdf_offsets[pdf]);
-    const int n = __builtin_amdgcn_readfirstlane(pdf_offsets[pdf + 1]) - m0;
-    const float *x = feats + static_cast<size_t>(row) * feat_stride;
-    float *out = post + entry_goff[ei];
-    float mx = -INFINITY;
-    for (int g = lane; g < n; g += 64) {
-      const float *mir = mi + static_cast<size_t>(m0 + g) * D;
-      const float *ivr = iv + static_cast<size_t>(m0 + g) * D;
-      float a1 = 0.f, a2 = 0.f;
-      for (int d = 0; d < D; d++) {
-        const float v = x[d];
-        a1 = fmaf(v, mir[d], a1);
-        a2 = fmaf(v * v, ivr[d], a2);   // data_sq.ApplyPow(2.0)
-      }
-      const float ll = (gconsts[m0 + g] + a1) + (-0.5f * a2);
-      out[g] = ll;
-      mx = fmaxf(mx, ll);
-    }
-    mx = kh_wave_max(mx);
-    float sum = 0.f;   // the same value in every lane
-    for (int g0 = 0; g0 < n; g0 += 64) {
-      const int g = g0 + lane;
-      float ev = 0.f;
-      if (g < n) {
-        ev = expf(out[g] - mx);
-        out[g] = ev;
-      }
-      const int cnt = n - g0 < 64 ? n - g0 : 64;
-      for (int j = 0; j < cnt; j++) sum += ReadLaneF(ev, j);   // sum += (data_[i] = Exp(data_[i] - max)), in order
-    }
-    const float inv = static_cast<float>(1.0 / static_cast<double>(sum));   // this->Scale(1.0 / sum)
-    const float w = entry_weight[ei];
-    for (int g = lane; g < n; g += 64) out[g] = (out[g] * inv) * w;          // posterior.Scale(weight)
-    if (lane == 0) like[ei] = mx + logf(sum);
-  }
-}
 
 // A2.
 __global__ void __launch_bounds__(64)
@@ -309,32 +225,6 @@ bool CheckOffsets32(const char *fn, const char *what, const int32_t *o, int n, i
   return true;
 }
 
-// The entry list against the model: frame_entry_offsets monotone from 0, pdfs in range and ascending within a frame is NOT
-// required here (the order is the caller's), Gaussian offsets = the running sum of the entries' pdf sizes.
-bool CheckEntries(const char *fn, int T, const int32_t *pdf_offsets, int num_pdfs, const int64_t *feo, const int32_t *entry_pdf,
-                  const int64_t *goff) {
-  if (feo[0] != 0) { SetError("%s: frame_entry_offsets[0] = %lld, not 0", fn, static_cast<long long>(feo[0])); return false; }
-  for (int t = 0; t < T; t++)
-    if (feo[t + 1] < feo[t]) { SetError("%s: frame_entry_offsets runs backwards at frame %d", fn, t); return false; }
-  const int64_t E = feo[T];
-  if (E >= (int64_t(1) << 31)) { SetError("%s: %lld entries, at most 2^31 - 1", fn, static_cast<long long>(E)); return false; }
-  if (pdf_offsets[0] != 0) { SetError("%s: pdf_offsets[0] = %d, not 0", fn, pdf_offsets[0]); return false; }
-  for (int j = 0; j < num_pdfs; j++)
-    if (pdf_offsets[j + 1] <= pdf_offsets[j]) { SetError("%s: pdf %d is empty or runs backwards", fn, j); return false; }
-  if (goff[0] != 0) { SetError("%s: entry_gauss_offsets[0] = %lld, not 0", fn, static_cast<long long>(goff[0])); return false; }
-  for (int64_t e = 0; e < E; e++) {
-    const int pdf = entry_pdf[e];
-    if (pdf < 0 || pdf >= num_pdfs) { SetError("%s: entry %lld names pdf %d, the model has %d", fn, static_cast<long long>(e), pdf, num_pdfs); return false; }
-    const int64_t n = goff[e + 1] - goff[e];
-    if (n != pdf_offsets[pdf + 1] - pdf_offsets[pdf]) {
-      SetError("%s: pdf %d has %d Gaussians in the model, entry %lld carries %lld posteriors", fn, pdf,
-               pdf_offsets[pdf + 1] - pdf_offsets[pdf], static_cast<long long>(e), static_cast<long long>(n));
-      return false;
-    }
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -343,34 +233,9 @@ int kh_gmm_component_posteriors(const float *feats, int T, int D, int feat_strid
                                 const float *means_invvars, const float *inv_vars, const int32_t *pdf_offsets, int num_pdfs,
                                 const int64_t *frame_entry_offsets, const int32_t *entry_pdf, const float *entry_weight,
                                 const int64_t *entry_gauss_offsets, float *gauss_post, float *entry_like) {
-  Clock clk;
-  int rc = EnsureDevice();
-  if (rc) return rc;
-  KH_CHECK_ARG(feats && gconsts && means_invvars && inv_vars && pdf_offsets && frame_entry_offsets && entry_gauss_offsets);
-  KH_CHECK_ARG(T > 0 && D > 0 && feat_stride >= D && num_pdfs > 0);
-  const int64_t E = frame_entry_offsets[T];
-  KH_CHECK_ARG(E == 0 || (entry_pdf && entry_weight && gauss_post && entry_like));
-  if (!CheckEntries("kh_gmm_component_posteriors", T, pdf_offsets, num_pdfs, frame_entry_offsets, entry_pdf, entry_gauss_offsets))
-    return KH_EINVAL;
-  g_ms[0] = 0.f;
-  if (E == 0) return KH_OK;
-  std::vector<int32_t> entry_row(E);
-  for (int t = 0; t < T; t++)
-    for (int64_t e = frame_entry_offsets[t]; e < frame_entry_offsets[t + 1]; e++) entry_row[e] = t;
-  Scratch sc;
-  const int32_t *d_off = sc.Upload(pdf_offsets, num_pdfs + 1);
-  const int32_t *d_row = sc.Upload(entry_row.data(), E);
-  const int32_t *d_pdf = sc.Upload(entry_pdf, E);
-  const float *d_w = sc.Upload(entry_weight, E);
-  const int64_t *d_goff = sc.Upload(entry_gauss_offsets, E + 1);
-  if (!d_off || !d_row || !d_pdf || !d_w || !d_goff) { SetError("kh_gmm_component_posteriors: out of device memory"); return KH_ENOMEM; }
-  const int blocks = static_cast<int>(std::min<int64_t>(DivUp64(E, kPostWaves), static_cast<int64_t>(NumCUs()) * 16));
-  hipLaunchKernelGGL(ComponentPosteriorsKernel, dim3(blocks), dim3(64 * kPostWaves), 0, Stream(), feats, feat_stride, D, gconsts,
-                     means_invvars, inv_vars, d_off, d_row, d_pdf, d_w, d_goff, static_cast<long long>(E), gauss_post, entry_like);
-  KH_LAUNCH_CHECK();
-  KH_HIP(hipStreamSynchronize(Stream()));   // the uploads' host arrays go out of scope
-  g_ms[0] = clk.Ms();
-  return KH_OK;
+  return ComponentPosteriors<false>("kh_gmm_component_posteriors", &g_ms[0], feats, T, D, feat_stride, gconsts, means_invvars,
+                                    inv_vars, pdf_offsets, num_pdfs, frame_entry_offsets, entry_pdf, entry_weight,
+                                    entry_gauss_offsets, gauss_post, entry_like);
 }
 
 int kh_fmllr_frame_stats(const float *feats, int T, int D, int feat_stride, const float *means_invvars, const float *inv_vars,
@@ -388,8 +253,12 @@ int kh_fmllr_frame_stats(const float *feats, int T, int D, int feat_stride, cons
   if (!CheckOffsets32(fn, "utt_row_offsets", utt_row_offsets, n_utts, T)) return KH_EINVAL;
   if (!CheckOffsets32(fn, "spk_utt_offsets", spk_utt_offsets, n_spk, n_utts)) return KH_EINVAL;
   const int64_t E = frame_entry_offsets[T];
-  KH_CHECK_ARG(E == 0 || (entry_pdf && gauss_post && a && b && count));
-  if (!CheckEntries(fn, T, pdf_offsets, num_pdfs, frame_entry_offsets, entry_pdf, entry_gauss_offsets)) return KH_EINVAL;
+  KH_CHECK_ARG(E <= 0 || (entry_pdf && gauss_post && a && b && count));
+  std::string err;
+  if (!kh_gmmacc::Check(T, pdf_offsets, num_pdfs, frame_entry_offsets, entry_pdf, entry_gauss_offsets, &err)) {
+    SetError("%s: %s", fn, err.c_str());
+    return KH_EINVAL;
+  }
   // the merged frames: needs the rows on the host
   std::vector<float> h(static_cast<size_t>(T) * D);
   KH_HIP(hipMemcpy2DAsync(h.data(), sizeof(float) * D, feats, sizeof(float) * feat_stride, sizeof(float) * D, T, hipMemcpyDeviceToHost, Stream()));
@@ -471,11 +340,9 @@ int kh_fmllr_accumulate(const float *feats, int T, int D, int feat_stride, const
   Scratch sc;
   const int32_t *d_run_row = sc.Upload(run_row, n_runs);
   if (!d_run_row) { SetError("%s: out of device memory", fn); return KH_ENOMEM; }
-  hipEvent_t ev0, ev1;
-  KH_HIP(hipEventCreate(&ev0));
-  if (hipError_t ee = hipEventCreate(&ev1); ee != hipSuccess) {
-    (void)hipEventDestroy(ev0);
-    SetError("%s: hipEventCreate failed: %s", fn, hipGetErrorString(ee));
+  KernelEvents ev;
+  if (hipError_t ee = ev.Init(); ee != hipSuccess) {
+    SetError(kEventsFailed, fn, hipGetErrorString(ee));
     return KH_EDEVICE;
   }
   float kernel_ms = 0.f;
@@ -505,32 +372,25 @@ int kh_fmllr_accumulate(const float *feats, int T, int D, int feat_stride, const
       rc2 = KH_ENOMEM;
       break;
     }
-    (void)hipEventRecord(ev0, Stream());
+    ev.Begin();
     if (!chunks.empty())
       hipLaunchKernelGGL(FmllrAccumulateKernel, dim3(static_cast<unsigned>(chunks.size()), DivUp(n_items, kAccWaves)), dim3(64 * kAccWaves), 0,
                          Stream(), feats, feat_stride, D, d_run_row, a, b, count, d_chunks, d_partial);
     hipLaunchKernelGGL(FmllrReduceKernel, dim3(static_cast<unsigned>(std::min<size_t>(DivUp64(S, 256), 1024)), std::min(ng, 4096)), dim3(256), 0,
                        Stream(), d_partial, d_spk_chunk, ng, static_cast<long long>(S), d_out);
-    (void)hipEventRecord(ev1, Stream());
+    ev.End();
     std::vector<double> h_out(S * ng);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * S * ng, hipMemcpyDeviceToHost, Stream());
-    if (e == hipSuccess) e = hipStreamSynchronize(Stream());
-    if (e != hipSuccess) {
+    if (hipError_t e = ev.Collect(h_out.data(), d_out, S * ng, &kernel_ms); e != hipSuccess) {
       SetError("%s: %s", fn, hipGetErrorString(e));
       rc2 = KH_EDEVICE;
       break;
     }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) kernel_ms += ms;
     for (int s = 0; s < ng; s++) {
       std::copy(h_out.begin() + S * s, h_out.begin() + S * s + gs, G + gs * (s0 + s));
       std::copy(h_out.begin() + S * s + gs, h_out.begin() + S * (s + 1), K + ks * (s0 + s));
     }
     s0 = s1;
   }
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
   if (rc2 != KH_OK) return rc2;
   g_ms[4] = kernel_ms;
   g_ms[5] = static_cast<float>(n_groups);

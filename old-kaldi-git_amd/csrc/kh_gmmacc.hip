@@ -9,7 +9,7 @@
 // S is never stored: a lane makes its element from one float of the x image in LDS (column D of the image holds 1), widened
 // to double; x * x of a widened float is exact, and so is the product of two widened floats.
 // v_mfma_f64_16x16x4_f64: A [lane & 15][k = lane >> 4], B [k = lane >> 4][lane & 15], one double per lane; C/D col = lane & 15,
-// row = (lane >> 4) + 4 * reg (the operand layout of FmllrAccumulateKernel, kh_fmllr.hip:35-40).
+// row = (lane >> 4) + 4 * reg (the operand layout of FmllrAccumulateKernel, stage B of kh_fmllr.hip's header).
 // The host sorts the entries by pdf (stable: frame order within a pdf, csrc/kh_gmmacc_plan.h) and cuts each pdf's run into
 // chunks of kChunk entries.  A workgroup is one (chunk, 16-Gaussian row tile): it stages kSub entries at a time - their x rows
 // and the tile's 16 posteriors - in LDS; its 4 waves are the column groups: wave w owns the 16-column tiles w, w + 4, w + 8,
@@ -18,24 +18,19 @@
 // inputs, and the grouping of pdfs under the workspace limit changes no sum.
 // Supported D: 1 ... 127 (16 column tiles = 256 columns >= 2 D + 1); KH_EINVAL above.
 //
-// The posteriors of this route, kh_gmm_acc_component_posteriors, one wave per entry: kh_gmm_component_posteriors' arithmetic
-// (kh_fmllr.hip: the k-ordered fmaf chains of the scores, float max, fl32(f - max), the float sum in Gaussian order, times
-// fl32(1.0 / sum), times the weight; like = max + log(sum)) with EXP and LOG as the float of the double function (the
-// device library's double exp / log, under 1 ulp in double, rounded to float) - which is how DiagGmm::ComponentPosteriors'
-// line-by-line restatement states them - where that kernel takes the device library's expf / logf (1 ulp in float).  The statistics are written to a file as floats and read by gmm-est: with 1-ulp posteriors a
-// mean accumulator whose addends cancel moved by several float ulps against the restatement; with these it does not.  The
-// double exp is one per D fmaf pairs.
+// The posteriors of this route, kh_gmm_acc_component_posteriors, one wave per entry: ComponentPosteriorsKernel<true> of
+// kh_gmmstats.h, whose header states the arithmetic and why EXP and LOG are the float of the double function here.
 // Static LDS of GmmAccumulateKernel: the x image kSub x kXs floats and the posterior image kSub x 16 floats:
 // 32 x 144 x 4 + 32 x 16 x 4 = 20480 bytes.  kXs = 144 = 16 mod 64: the four entries of a fragment, 16 consecutive columns
 // each, fall on four disjoint runs of 16 banks.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "kh_common.h"
 #include "kh_gmmacc_plan.h"
+#include "kh_gmmstats.h"
 
 using namespace kh;
 
@@ -44,86 +39,6 @@ namespace {
 thread_local float g_ms[4] = {0.f, 0.f, 0.f, 0.f};   // acc_stats: whole call; host plan; the two kernels (device events); the posteriors' call
 thread_local int32_t g_counts[3] = {0, 0, 0};      // groups; chunks; workgroups of the accumulate kernel
 thread_local size_t g_ws_limit = 0;                // kh_gmm_acc_set_workspace_limit
-
-struct Clock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  float Ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
-// Device buffers of one call, returned to the pool on every exit.
-struct Scratch {
-  std::vector<void *> ptrs;
-  template <typename T> T *Get(size_t n) {
-    void *p = PoolMalloc(sizeof(T) * std::max<size_t>(n, 1));
-    if (p) ptrs.push_back(p);
-    return static_cast<T *>(p);
-  }
-  template <typename T> T *Upload(const T *host, size_t n) {
-    T *p = Get<T>(n);
-    if (p && n && hipMemcpyAsync(p, host, sizeof(T) * n, hipMemcpyHostToDevice, Stream()) != hipSuccess) return nullptr;
-    return p;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(Stream());
-    for (void *p : ptrs) PoolFree(p);
-  }
-};
-
-constexpr int kPostWaves = 4;
-
-__device__ __forceinline__ float ReadLaneF(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// post is read back only by the lane that wrote the element.
-__global__ void __launch_bounds__(64 * kPostWaves)
-GmmAccPosteriorsKernel(const float *__restrict__ feats, int feat_stride, int D, const float *__restrict__ gconsts,
-                       const float *__restrict__ mi, const float *__restrict__ iv, const int32_t *__restrict__ pdf_offsets,
-                       const int32_t *__restrict__ entry_row, const int32_t *__restrict__ entry_pdf,
-                       const float *__restrict__ entry_weight, const int64_t *__restrict__ entry_goff, long long E,
-                       float *post, float *__restrict__ like) {
-  const int lane = threadIdx.x & 63;
-  for (long long e0 = static_cast<long long>(blockIdx.x) * kPostWaves + (threadIdx.x >> 6); e0 < E;
-       e0 += static_cast<long long>(gridDim.x) * kPostWaves) {
-    const int ei = __builtin_amdgcn_readfirstlane(static_cast<int>(e0));   // E < 2^31, checked by the host
-    const int row = __builtin_amdgcn_readfirstlane(entry_row[ei]);
-    const int pdf = __builtin_amdgcn_readfirstlane(entry_pdf[ei]);
-    const int m0 = __builtin_amdgcn_readfirstlane(pdf_offsets[pdf]);
-    const int n = __builtin_amdgcn_readfirstlane(pdf_offsets[pdf + 1]) - m0;
-    const float *x = feats + static_cast<size_t>(row) * feat_stride;
-    float *out = post + entry_goff[ei];
-    float mx = -INFINITY;
-    for (int g = lane; g < n; g += 64) {
-      const float *mir = mi + static_cast<size_t>(m0 + g) * D;
-      const float *ivr = iv + static_cast<size_t>(m0 + g) * D;
-      float a1 = 0.f, a2 = 0.f;
-      for (int d = 0; d < D; d++) {
-        const float v = x[d];
-        a1 = fmaf(v, mir[d], a1);
-        a2 = fmaf(v * v, ivr[d], a2);   // data_sq.ApplyPow(2.0)
-      }
-      const float ll = (gconsts[m0 + g] + a1) + (-0.5f * a2);
-      out[g] = ll;
-      mx = fmaxf(mx, ll);
-    }
-    mx = kh_wave_max(mx);
-    float sum = 0.f;   // the same value in every lane
-    for (int g0 = 0; g0 < n; g0 += 64) {
-      const int g = g0 + lane;
-      float ev = 0.f;
-      if (g < n) {
-        ev = static_cast<float>(exp(static_cast<double>(out[g] - mx)));
-        out[g] = ev;
-      }
-      const int cnt = n - g0 < 64 ? n - g0 : 64;
-      for (int j = 0; j < cnt; j++) sum += ReadLaneF(ev, j);   // sum += (data_[i] = Exp(data_[i] - max)), in order
-    }
-    const float inv = static_cast<float>(1.0 / static_cast<double>(sum));   // this->Scale(1.0 / sum)
-    const float w = entry_weight[ei];
-    for (int g = lane; g < n; g += 64) out[g] = (out[g] * inv) * w;          // posteriors.Scale(weight)
-    if (lane == 0) like[ei] = mx + static_cast<float>(log(static_cast<double>(sum)));
-  }
-}
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kChunk = 256;          // entries per chunk (tests/gmm_acc_cases.py: CHUNK)
@@ -232,38 +147,9 @@ int kh_gmm_acc_component_posteriors(const float *feats, int T, int D, int feat_s
                                     const float *means_invvars, const float *inv_vars, const int32_t *pdf_offsets, int num_pdfs,
                                     const int64_t *frame_entry_offsets, const int32_t *entry_pdf, const float *entry_weight,
                                     const int64_t *entry_gauss_offsets, float *gauss_post, float *entry_like) {
-  Clock clk;
-  int rc = EnsureDevice();
-  if (rc) return rc;
-  const char *fn = "kh_gmm_acc_component_posteriors";
-  KH_CHECK_ARG(feats && gconsts && means_invvars && inv_vars && pdf_offsets && frame_entry_offsets && entry_gauss_offsets);
-  KH_CHECK_ARG(T > 0 && D > 0 && feat_stride >= D && num_pdfs > 0);
-  const int64_t E = frame_entry_offsets[T];
-  KH_CHECK_ARG(E <= 0 || (entry_pdf && entry_weight && gauss_post && entry_like));
-  std::string err;
-  if (!kh_gmmacc::Check(T, pdf_offsets, num_pdfs, frame_entry_offsets, entry_pdf, entry_gauss_offsets, &err)) {
-    SetError("%s: %s", fn, err.c_str());
-    return KH_EINVAL;
-  }
-  g_ms[3] = 0.f;
-  if (E == 0) return KH_OK;
-  std::vector<int32_t> entry_row(E);
-  for (int t = 0; t < T; t++)
-    for (int64_t e = frame_entry_offsets[t]; e < frame_entry_offsets[t + 1]; e++) entry_row[e] = t;
-  Scratch sc;
-  const int32_t *d_off = sc.Upload(pdf_offsets, num_pdfs + 1);
-  const int32_t *d_row = sc.Upload(entry_row.data(), E);
-  const int32_t *d_pdf = sc.Upload(entry_pdf, E);
-  const float *d_w = sc.Upload(entry_weight, E);
-  const int64_t *d_goff = sc.Upload(entry_gauss_offsets, E + 1);
-  if (!d_off || !d_row || !d_pdf || !d_w || !d_goff) { SetError("%s: out of device memory", fn); return KH_ENOMEM; }
-  const int blocks = static_cast<int>(std::min<int64_t>(DivUp64(E, kPostWaves), static_cast<int64_t>(NumCUs()) * 16));
-  hipLaunchKernelGGL(GmmAccPosteriorsKernel, dim3(blocks), dim3(64 * kPostWaves), 0, Stream(), feats, feat_stride, D, gconsts,
-                     means_invvars, inv_vars, d_off, d_row, d_pdf, d_w, d_goff, static_cast<long long>(E), gauss_post, entry_like);
-  KH_LAUNCH_CHECK();
-  KH_HIP(hipStreamSynchronize(Stream()));   // the uploads' host arrays go out of scope
-  g_ms[3] = clk.Ms();
-  return KH_OK;
+  return ComponentPosteriors<true>("kh_gmm_acc_component_posteriors", &g_ms[3], feats, T, D, feat_stride, gconsts, means_invvars,
+                                   inv_vars, pdf_offsets, num_pdfs, frame_entry_offsets, entry_pdf, entry_weight,
+                                   entry_gauss_offsets, gauss_post, entry_like);
 }
 
 int kh_gmm_acc_stats(const float *feats, int T, int D, int feat_stride, const int32_t *pdf_offsets, int num_pdfs,
@@ -310,11 +196,9 @@ int kh_gmm_acc_stats(const float *feats, int T, int D, int feat_stride, const in
   const int32_t *d_row = sc.Upload(plan.sorted_row.data(), E);
   const int64_t *d_goff = sc.Upload(sorted_goff.data(), E);
   if (!d_row || !d_goff) { SetError("%s: out of device memory", fn); return KH_ENOMEM; }
-  hipEvent_t ev0, ev1;
-  KH_HIP(hipEventCreate(&ev0));
-  if (hipError_t ee = hipEventCreate(&ev1); ee != hipSuccess) {
-    (void)hipEventDestroy(ev0);
-    SetError("%s: hipEventCreate failed: %s", fn, hipGetErrorString(ee));
+  KernelEvents ev;
+  if (hipError_t ee = ev.Init(); ee != hipSuccess) {
+    SetError(kEventsFailed, fn, hipGetErrorString(ee));
     return KH_EDEVICE;
   }
   float kernel_ms = 0.f;
@@ -349,23 +233,18 @@ int kh_gmm_acc_stats(const float *feats, int T, int D, int feat_stride, const in
       rc2 = KH_ENOMEM;
       break;
     }
-    (void)hipEventRecord(ev0, Stream());
+    ev.Begin();
     hipLaunchKernelGGL(GmmAccumulateKernel, dim3(static_cast<unsigned>(blocks.size())), dim3(64 * kAccWaves), 0, Stream(), feats,
                        feat_stride, D, C, d_row, d_goff, gauss_post, d_blocks, d_partial);
     hipLaunchKernelGGL(GmmAccReduceKernel, dim3(static_cast<unsigned>(std::min<size_t>(pdfs.size(), 65536))), dim3(256), 0, Stream(),
                        d_partial, d_pdfs, static_cast<int>(pdfs.size()), d_out);
-    (void)hipEventRecord(ev1, Stream());
+    ev.End();
     std::vector<double> h_out(out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * out, hipMemcpyDeviceToHost, Stream());
-    if (e == hipSuccess) e = hipStreamSynchronize(Stream());
-    if (e != hipSuccess) {
+    if (hipError_t e = ev.Collect(h_out.data(), d_out, out, &kernel_ms); e != hipSuccess) {
       SetError("%s: %s", fn, hipGetErrorString(e));
       rc2 = KH_EDEVICE;
       break;
     }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) kernel_ms += ms;
     const double *src = h_out.data();
     for (int g = pdf_offsets[gr.pdf_begin]; g < pdf_offsets[gr.pdf_end]; g++, src += C) {
       occ[g] = src[0];
@@ -373,8 +252,6 @@ int kh_gmm_acc_stats(const float *feats, int T, int D, int feat_stride, const in
       if (vars) std::copy(src + 1 + D, src + 1 + 2 * D, var_acc + static_cast<size_t>(g) * D);
     }
   }
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
   if (rc2 != KH_OK) return rc2;
   g_ms[2] = kernel_ms;
   g_counts[0] = static_cast<int32_t>(groups.size());

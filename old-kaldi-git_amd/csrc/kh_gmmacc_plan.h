@@ -1,7 +1,9 @@
 // kh_gmmacc_plan.h - the host plan of kh_gmm_acc_stats (csrc/kh_gmmacc.hip): plain C++, no HIP, so that the checks, the sort,
 // the chunks and the groups are tested on the CPU (tests/test_gmmacc_plan_host.py).
 //
-//   Check    every offset and index of the call, as kh_gmm_component_posteriors checks them; the message names the pdf or entry
+//   Check    every offset and index of an entry list against the model; the message names the pdf or entry.  The one check of
+//            every route that takes an entry list: the two posteriors calls (kh_gmmstats.h), kh_fmllr_frame_stats,
+//            kh_gmm_acc_stats and kh_mllt_acc_stats.  Pdfs ascending within a frame is NOT required (the order is the caller's).
 //   Sort     a stable counting sort of the entries by pdf: within a pdf the entries stay in entry (= frame) order
 //   chunks   a pdf's run of n entries is cut into DivUp(n, chunk) chunks of at most `chunk` entries (a run of 0: no chunk)
 //   Groups   consecutive pdfs whose workspace - (chunks + 1) * G * C doubles per pdf: one partial sum per chunk and the sum -

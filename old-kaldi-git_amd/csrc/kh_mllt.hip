@@ -14,7 +14,7 @@
 // is given, and the library's flags (build.py: -fno-fast-math, -ffp-contract=off) do not give it; fp32 denormals are kept
 // on gfx9.  tests/test_gpu_mllt.py holds the result to a bound that a 1-ulp o or w breaks by orders of magnitude.
 // v_mfma_f64_16x16x4_f64: A [lane & 15][k = lane >> 4], B [k = lane >> 4][lane & 15], one double per lane; C/D col = lane & 15,
-// row = (lane >> 4) + 4 * reg (the operand layout of FmllrAccumulateKernel, kh_fmllr.hip:35-40, and GmmAccumulateKernel).
+// row = (lane >> 4) + 4 * reg (the operand layout of FmllrAccumulateKernel, stage B of kh_fmllr.hip's header, and GmmAccumulateKernel).
 //
 // The host makes the item list - (row, Gaussian, posterior) with a nonzero posterior, in entry order then Gaussian order -
 // and cuts it into slices of  slice_len = kChunk * max(1, ceil(n / (kChunk * kMaxSlices)))  items: a function of n and the
@@ -37,7 +37,6 @@
 // when it initialises and draws from it at some first uses; seen on an MI355X), so a caller that wants the reference's
 // sequence positions it at every call.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
@@ -46,6 +45,7 @@
 
 #include "kh_common.h"
 #include "kh_gmmacc_plan.h"
+#include "kh_gmmstats.h"
 
 using namespace kh;
 
@@ -54,30 +54,6 @@ namespace {
 thread_local float g_ms[3] = {0.f, 0.f, 0.f};   // whole call; host plan (checks, download of the posteriors, item list); kernels (events)
 thread_local int32_t g_counts[3] = {0, 0, 0};   // items; slices; workgroups of the accumulate kernel
 std::mutex g_rand_mutex;
-
-struct Clock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  float Ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
-// Device buffers of one call, returned to the pool on every exit.
-struct Scratch {
-  std::vector<void *> ptrs;
-  template <typename T> T *Get(size_t n) {
-    void *p = PoolMalloc(sizeof(T) * std::max<size_t>(n, 1));
-    if (p) ptrs.push_back(p);
-    return static_cast<T *>(p);
-  }
-  template <typename T> T *Upload(const T *host, size_t n) {
-    T *p = Get<T>(n);
-    if (p && n && hipMemcpyAsync(p, host, sizeof(T) * n, hipMemcpyHostToDevice, Stream()) != hipSuccess) return nullptr;
-    return p;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(Stream());
-    for (void *p : ptrs) PoolFree(p);
-  }
-};
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kChunk = 256;          // items per slice, times a whole number (tests/mllt_cases.py restates the rule)
@@ -281,14 +257,12 @@ int kh_mllt_acc_stats(const float *feats, int T, int D, int feat_stride, const f
     SetError("%s: out of device memory (%d items, %d slices)", fn, n, n_slices);
     return KH_ENOMEM;
   }
-  hipEvent_t ev0, ev1;
-  KH_HIP(hipEventCreate(&ev0));
-  if (hipError_t ee = hipEventCreate(&ev1); ee != hipSuccess) {
-    (void)hipEventDestroy(ev0);
-    SetError("%s: hipEventCreate failed: %s", fn, hipGetErrorString(ee));
+  KernelEvents ev;
+  if (hipError_t ee = ev.Init(); ee != hipSuccess) {
+    SetError(kEventsFailed, fn, hipGetErrorString(ee));
     return KH_EDEVICE;
   }
-  (void)hipEventRecord(ev0, Stream());
+  ev.Begin();
   const dim3 grid(n_slices, GG);
   switch (RT) {
     case 1: LaunchAccumulate<1>(grid, feats, feat_stride, D, means_invvars, inv_vars, d_row, d_gauss, d_p, n, slice_len, d_partial); break;
@@ -297,15 +271,9 @@ int kh_mllt_acc_stats(const float *feats, int T, int D, int feat_stride, const f
     default: LaunchAccumulate<kMaxRT>(grid, feats, feat_stride, D, means_invvars, inv_vars, d_row, d_gauss, d_p, n, slice_len, d_partial); break;
   }
   hipLaunchKernelGGL(MlltReduceKernel, dim3(DivUp(size, 256)), dim3(256), 0, Stream(), d_partial, n_slices, size, d_out);
-  (void)hipEventRecord(ev1, Stream());
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(G, d_out, sizeof(double) * size, hipMemcpyDeviceToHost, Stream());
-  if (e == hipSuccess) e = hipStreamSynchronize(Stream());
+  ev.End();
   float ms = 0.f;
-  if (e == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess) ms = 0.f;
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
-  if (e != hipSuccess) {
+  if (hipError_t e = ev.Collect(G, d_out, size, &ms); e != hipSuccess) {
     SetError("%s: %s", fn, hipGetErrorString(e));
     return KH_EDEVICE;
   }

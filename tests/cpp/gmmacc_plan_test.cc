@@ -171,6 +171,22 @@ int main() {
   { Case b = small; b.pdf_offsets = {0, 2, 2}; refused(b, "pdf 1 is empty or runs backwards"); }
   { Case b = small; b.pdf_offsets[0] = 1; refused(b, "pdf_offsets[0] = 1, not 0"); }
   { Case b = small; b.goff[0] = 1; refused(b, "entry_gauss_offsets[0] = 1, not 0"); }
+  // no entries: entry_gauss_offsets[0] is not looked at
+  {
+    Case d;
+    d.pdf_offsets = {0, 2, 3};
+    d.feo = {0, 0, 0};
+    d.goff = {7};
+    EXPECT(d.Check(&err));
+  }
+  // a negative frame_entry_offsets[T] runs backwards somewhere; the entry arrays (null here) are not touched
+  {
+    const std::vector<int32_t> off = {0, 2, 3};
+    const std::vector<int64_t> feo = {0, 0, -1};
+    std::string e;
+    EXPECT(!kh_gmmacc::Check(2, off.data(), 2, feo.data(), nullptr, nullptr, &e));
+    EXPECT(e == "frame_entry_offsets runs backwards at frame 1");
+  }
   if (failures) {
     std::printf("%d failures\n", failures);
     return 1;

@@ -35,8 +35,8 @@ import numpy as np
 import fmllr_restatement as R
 import gmm_cases
 
-FRAME_CHUNK = 256      # kFrameChunk, kh_fmllr.hip:178: merged frames per workgroup of FmllrAccumulateKernel
-MAX_DIM = 63           # kMaxD, kh_fmllr.hip:183
+FRAME_CHUNK = 256      # kFrameChunk, csrc/kh_fmllr.hip: merged frames per workgroup of FmllrAccumulateKernel
+MAX_DIM = 63           # kMaxD, csrc/kh_fmllr.hip
 U = 2.0 ** -24
 
 

@@ -19,7 +19,8 @@ elementwise to equal or adjacent floats; the count of unequal elements is printe
 |sum t_e|, where the bounds above are relative to sum |t_e|.  With stage A1's posteriors (the device library's expf: 5 % of
 them 1 - 3 float ulps from the restatement's) mean_acc elements whose addends cancel, sum |t_e| / |sum t_e| of 76 - 146, were
 2 - 4 float ulps apart.  The route therefore takes its posteriors from kh_gmm_acc_component_posteriors, whose exp and log are
-the float of the double function, as the restatement states them; what is left between the two routes is the summation order, (n + 2) 2^-53
+the float of the double function, as the restatement states them (ComponentPosteriorsKernel<true> where A1 is <false>; the one
+statement of both is the header of csrc/kh_gmmstats.h); what is left between the two routes is the summation order, (n + 2) 2^-53
 sum |t_e| each, which moves a float by more than one ulp only under cancellation by 2^28 / n."""
 from fractions import Fraction
 

@@ -19,10 +19,12 @@ def test_gmmacc_kernel_resources(tmp_path):
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     names = re.findall(r"Function Name: (\S+)", p.stderr)
-    n_kernels = len(re.findall(r"^__global__", text, flags=re.M))
+    # two kernels of its own and the shared posterior kernel (csrc/kh_gmmstats.h), of which it compiles <true> alone
+    shared = open(os.path.join(os.path.dirname(src), "kh_gmmstats.h")).read()
+    n_kernels = len(re.findall(r"^__global__", text + shared, flags=re.M))
     assert n_kernels == 3 and len(names) == 3, names
-    for k in ("GmmAccPosteriorsKernel", "GmmAccumulateKernel", "GmmAccReduceKernel"):
-        assert any(k in n for n in names), k
+    for k in ("ComponentPosteriorsKernelILb1EE", "GmmAccumulateKernel", "GmmAccReduceKernel"):
+        assert sum(k in n for n in names) == 1, k
     get = lambda what: [int(x) for x in re.findall(re.escape(what) + r":\s*(\d+)", p.stderr)]
     print("kernels", names, "VGPRs", get("VGPRs"), "AGPRs", get("AGPRs"), "SGPRs", get("SGPRs"), "LDS", get("LDS Size [bytes/block]"),
           "scratch", get("ScratchSize [bytes/lane]"), "occupancy", get("Occupancy [waves/SIMD]"))
@@ -36,4 +38,4 @@ def test_gmmacc_kernel_resources(tmp_path):
     assert re.search(r"constexpr int kSub = %s;" % m.group(1), text) and re.search(r"constexpr int kXs = %s;" % m.group(2), text)
     assert [v for n, v in lds.items() if "GmmAccumulateKernel" in n] == [20480]
     assert [v for n, v in lds.items() if "GmmAccumulateKernel" not in n] == [0, 0]
-    assert "atomic" not in re.sub(r"//.*", "", text)
+    assert "atomic" not in re.sub(r"//.*", "", text + shared)

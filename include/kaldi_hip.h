@@ -1408,6 +1408,41 @@ int kh_mllt_max_dim(void);
  * kernel (slices x groups of 16 column tiles). */
 int kh_mllt_last_timings(float *ms, int32_t *counts);
 
+/* ------------------------------------------------------------------ LDA statistics (csrc/kh_lda.hip)
+ * acc-lda for a batch of stacked frames: LdaEstimate::Accumulate (transform/lda-estimate.cc:45-55) for every (frame, pdf,
+ * weight) entry whose weight is not zero (-0.0 is zero), the weights being those RandPrune has ALREADY been applied to
+ * (kh_rand_prune_at).  feats (DEVICE, T x D, row pitch feat_stride); the entry list is HOST: frame_entry_offsets [T + 1],
+ * entry_pdf [E], entry_weight [E].  segment_frame_offsets [num_segments + 1] (HOST): the utterances of the call, from 0 to T
+ * (NULL: one segment).  Per item, w and x widened to double,
+ *     zero[c] += w,   first[c][d] += w x[d],   second[a (a + 1) / 2 + b] += (w x[a]) x[b]   for a >= b,
+ * HOST outputs zero [num_classes], first [num_classes x D], second [D (D + 1) / 2] packed as SpMatrix packs.  add == 0: the
+ * outputs are SET; add != 0: the sums are added to what they hold.  T = 0 or no item: zeros, or unchanged under add.
+ * The sum tree depends on the input alone.  The items are in entry order.  `second`: a segment's items are cut into slices of
+ *     kh_lda_chunk * max(1, ceil(n_seg / (kh_lda_chunk * kh_lda_max_slices)))
+ * items, per slice the lower triangle of an fp64 matrix-core X^T diag(w) X with both operands made on the fly; a segment's
+ * sum is its slices' partial sums added in slice order from zero, and the segments' sums are added one after another in
+ * segment order onto (add ? the buffer : zero).  `first`, `zero`: per (segment, class) the class's items in entry order in
+ * chunks of kh_lda_chunk, the chunks' partial sums added in chunk order from zero, then the segments in order in the same
+ * way.  No atomics: the same input gives the same bits, and a job gives the same bits however its segments are grouped into
+ * calls that run on from one another with add.  D = 1 ... kh_lda_max_dim (512).  Before any launch, KH_EINVAL naming the
+ * offender: D above the limit, a pdf outside 0 .. num_classes - 1, offsets that run backwards, segments that do not run from
+ * 0 to T. */
+int kh_lda_acc_stats(const float *feats, int T, int D, int feat_stride, const int64_t *frame_entry_offsets, const int32_t *entry_pdf,
+                     const float *entry_weight, int num_classes, const int64_t *segment_frame_offsets, int num_segments, int add,
+                     double *zero, double *first, double *second);
+/* The slices' partial sums (D (D + 1) / 2 doubles each) go to a workspace of at most this many bytes (calling thread; 0 = the
+ * default, 1 GiB): a call is cut into passes over runs of whole slices, one accumulation and one reduction launch per pass.
+ * No sum depends on it.  A limit below one slice's partial sums: kh_lda_acc_stats returns KH_ENOMEM naming the bytes needed,
+ * before any launch. */
+int kh_lda_set_workspace_limit(size_t bytes);
+int kh_lda_chunk(void);
+int kh_lda_max_slices(void);
+int kh_lda_max_dim(void);
+/* ms[3]: milliseconds of the calling thread's last kh_lda_acc_stats: the whole call, its host plan (checks, item list, slices,
+ * sort by class), its kernels alone (device events).  counts[4]: items, slices, workgroups of the accumulation kernel (slices
+ * x pairs of 64-column super tiles), passes. */
+int kh_lda_last_timings(float *ms, int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

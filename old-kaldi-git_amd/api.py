@@ -3642,6 +3642,122 @@ def add_mllt_stats(into, acc):
         raise KhError(str(e))
 
 
+# ---------------------------------------------------------------- LDA statistics (csrc/kh_lda.hip)
+# acc-lda for stacked frames.  An accumulator is dict(zero [C], first [C, D], second [D (D + 1) / 2] packed as SpMatrix packs,
+# all float64; dim, num_classes); accumulate_lda_stats adds draws.  The entry list needs feo, pdf and weight only.
+_LDA_MISMATCH = "LdaEstimate::Read, dimension or classes count mismatch, %d, %d,  vs. %d, %d"
+
+
+def lda_acc_stats(feats, ent, num_classes, segments=None, into=None):
+    """LdaEstimate::Accumulate (transform/lda-estimate.cc:45-55) for every entry whose weight is not zero, the weights being
+    those RandPrune has already been applied to (kh_lda_acc_stats): one library call, whatever the number of segments.
+    feats: 2-D float32 device tensor of at most lda_max_dim() columns; ent: dict(feo [T + 1], pdf [E], weight [E]);
+    segments: row offsets [S + 1] of the call's utterances, from 0 to T (None: one segment).  into: an accumulator this
+    function returned (dim and num_classes must agree): the library runs on from its buffers, segment after segment, so a
+    job gives the same bits however its utterances are grouped into calls.  Returns dict(zero, first, second, dim,
+    num_classes)."""
+    T, D, stride = _feat_args(feats)
+    C_ = int(num_classes)
+    feo = np.ascontiguousarray(ent["feo"], np.int64)
+    pdf = np.ascontiguousarray(ent["pdf"], np.int32)
+    w = np.ascontiguousarray(ent["weight"], np.float32)
+    if len(feo) != T + 1 or len(w) != len(pdf):
+        raise KhError("lda_acc_stats: entry list of %d frames / %d entries / %d weights against %d frames" % (len(feo) - 1, len(pdf), len(w), T))
+    if len(pdf) < int(feo.max()):
+        raise KhError("lda_acc_stats: frame_entry_offsets reach %d, the list holds %d entries" % (int(feo.max()), len(pdf)))
+    seg = np.ascontiguousarray([0, T] if segments is None else segments, np.int64).reshape(-1)
+    if len(seg) < 1:
+        raise KhError("lda_acc_stats: segments need at least one offset")
+    if into is None:
+        if C_ <= 0:
+            raise KhError("lda_acc_stats: %d classes" % C_)
+        acc = dict(zero=np.zeros(C_, np.float64), first=np.zeros((C_, D), np.float64), second=np.zeros(D * (D + 1) // 2, np.float64),
+                   dim=D, num_classes=C_)
+    else:
+        acc = into
+        if int(acc["dim"]) != D or int(acc["num_classes"]) != C_:
+            raise KhError(_LDA_MISMATCH % (int(acc["num_classes"]), int(acc["dim"]), C_, D))
+        for k, shape in (("zero", (C_,)), ("first", (C_, D)), ("second", (D * (D + 1) // 2,))):
+            a = acc[k]
+            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous or a.shape != shape:
+                raise KhError("lda_acc_stats: into[%r] must be a contiguous float64 array of shape %r" % (k, shape))
+    dp, ip, lp = capi.c_double_p, capi.c_int32_p, capi.c_int64_p
+    check(lib().kh_lda_acc_stats(_p(feats), T, D, stride, feo.ctypes.data_as(lp), pdf.ctypes.data_as(ip), w.ctypes.data_as(capi.c_float_p),
+                                 C_, seg.ctypes.data_as(lp), len(seg) - 1, 0 if into is None else 1, acc["zero"].ctypes.data_as(dp),
+                                 acc["first"].ctypes.data_as(dp), acc["second"].ctypes.data_as(dp)))
+    return acc
+
+
+def lda_chunk():
+    """Items per slice of the LDA accumulation, times a whole number, and items per chunk of its first-order sums (kChunk of
+    csrc/kh_lda.hip)."""
+    return int(lib().kh_lda_chunk())
+
+
+def lda_max_slices():
+    return int(lib().kh_lda_max_slices())
+
+
+def lda_max_dim():
+    return int(lib().kh_lda_max_dim())
+
+
+def lda_set_workspace_limit(nbytes):
+    """lda_acc_stats takes the slices in passes whose workspace stays within nbytes (calling thread; 0 = 1 GiB)."""
+    check(lib().kh_lda_set_workspace_limit(int(nbytes)))
+
+
+def lda_last_timings():
+    """The calling thread's last lda_acc_stats: milliseconds of the call, its host plan and its kernels; items, slices,
+    workgroups, passes."""
+    return _timings(lib().kh_lda_last_timings, ("call_ms", "plan_ms", "kernels_ms"), ("items", "slices", "workgroups", "passes"))
+
+
+def lda_entries(pdf_posts):
+    """The entry list of a Posterior over pdfs for lda_acc_stats: dict(feo, pdf, weight), each frame in the order given."""
+    feo = np.zeros(len(pdf_posts) + 1, np.int64)
+    pdf, w = [], []
+    for t, fr in enumerate(pdf_posts):
+        for p, x in fr:
+            pdf.append(int(p))
+            w.append(x)
+        feo[t + 1] = len(pdf)
+    return dict(feo=feo, pdf=np.ascontiguousarray(pdf, np.int32), weight=np.ascontiguousarray(w, np.float32))
+
+
+def accumulate_lda_stats(feats, pdf_posts, num_pdfs, rand_prune=0.0, seed=None, into=None, segments=None):
+    """The loop of bin/acc-lda.cc:99-110 for every (frame, pdf, weight) of the stacked frames: RandPrune on the weights on the
+    host, strictly in utterance, frame, entry order, then lda_acc_stats - one library call.  pdf_posts: [(pdf, weight), ...]
+    per frame (convert_posterior_to_pdfs: ascending pdfs).  rand_prune defaults to 0.0 as the binary's option does.
+    seed None: the pruning draws from the C library's generator as it stands.  seed s: the job's draws are those of
+    srand(s), and this call's begin where into's ended (rand_prune_at with into["draws"]): 1 gives what a reference binary
+    draws, however the job is cut into calls.  into, segments: as lda_acc_stats.  Returns dict(zero, first, second, dim,
+    num_classes, draws), draws the job's so far."""
+    thresh = float(rand_prune)
+    ent = lda_entries(pdf_posts)
+    before = 0 if into is None else int(into.get("draws", 0))
+    w = ent["weight"]
+    if not thresh >= 0:
+        raise KhError("rand_prune: prune threshold %g, must be >= 0" % thresh)
+    if seed is None:
+        draws = int(((w != 0) & (np.abs(w) < np.float32(thresh))).sum())      # one draw for each such value
+        _rand_prune(w, thresh)
+    else:
+        draws = rand_prune_at(w, thresh, seed, before)
+    acc = lda_acc_stats(feats, ent, num_pdfs, segments=segments, into=into)
+    acc["draws"] = before + draws
+    return acc
+
+
+def add_lda_stats(into, acc):
+    """into += acc in double, as LdaEstimate::Read with add = true, with its mismatch message."""
+    from . import kaldi_io
+    try:
+        return kaldi_io.add_lda_accs(into, acc)
+    except ValueError as e:
+        raise KhError(str(e))
+
+
 # ---- host posterior / transform algebra of the fMLLR recipes
 def weight_silence_post(tid2phone, silence_phones, silence_scale, post, distribute=False):
     """WeightSilencePost / WeightSilencePostDistributed (hmm/posterior.cc:361-413): tid2phone indexed by transition-id."""

@@ -2010,3 +2010,106 @@ def read_config_file(path):
             k, _, v = line[2:].partition("=")
             out[k.strip()] = v.strip() if _ else "true"
     return out
+
+
+# ---------------------------------------------------------------- LDA accumulators (the .acc files between acc-lda and est-lda)
+# An accumulator is dict(zero [C] float64, first [C, D] float64, second [D (D + 1) / 2] float64 - the packed lower triangle
+# of total_second_acc_ -, dim, num_classes); nothing accumulated: dim 0, 0 classes.
+def empty_lda_accs():
+    return dict(zero=np.zeros(0, np.float64), first=np.zeros((0, 0), np.float64), second=np.zeros(0, np.float64), dim=0, num_classes=0)
+
+
+def _lda_mangle(second, zero, first, sign):
+    """second + sign * sum over c ascending with zero[c] != 0 of first_c first_c^T / zero[c], each class one packed
+    AddVec2(sign / zero[c], first_c): per element  ap[r (r + 1) / 2 + c] += x[c] * (alpha * x[r])."""
+    out = np.array(second, np.float64)
+    r, c = np.tril_indices(first.shape[1] if first.ndim == 2 else 0)
+    for k in range(len(zero)):
+        if zero[k] != 0:
+            x = first[k]
+            out += x[c] * ((sign / zero[k]) * x[r])
+    return out
+
+
+def write_lda_accs(f, acc, binary=True):
+    """LdaEstimate::Write (transform/lda-estimate.cc:237-260): the counts and the first-order rows cast to float; the
+    second-order matrix "mangled" in double - minus first_c first_c^T / zero_c over the classes with a count - and then
+    cast to a float SpMatrix."""
+    dim, nc = int(acc["dim"]), int(acc["num_classes"])
+    zero = np.asarray(acc["zero"], np.float64).reshape(nc)
+    first = np.asarray(acc["first"], np.float64).reshape(nc, dim)
+    second = np.asarray(acc["second"], np.float64).reshape(dim * (dim + 1) // 2)
+    write_token(f, binary, "<LDAACCS>")
+    write_token(f, binary, "<VECSIZE>")
+    write_int32(f, binary, dim)
+    write_token(f, binary, "<NUMCLASSES>")
+    write_int32(f, binary, nc)
+    write_token(f, binary, "<ZERO_ACCS>")
+    write_vector(f, zero.astype(np.float32), binary)
+    write_token(f, binary, "<FIRST_ACCS>")
+    write_matrix(f, first.astype(np.float32), binary)
+    write_token(f, binary, "<SECOND_ACCS>")
+    with np.errstate(over="ignore", invalid="ignore"):
+        write_sp_matrix(f, _packed_to_full(_lda_mangle(second, zero, first, -1.0), dim).astype(np.float32), binary)
+    write_token(f, binary, "</LDAACCS>")
+
+
+def add_lda_accs(into, acc):
+    """into += acc in double, as LdaEstimate::Read with add = true (lda-estimate.cc:190-199), with its message; an
+    accumulator of dim 0 and 0 classes takes the other's sizes."""
+    if int(into["num_classes"]) != 0 or int(into["dim"]) != 0:
+        if int(acc["num_classes"]) != int(into["num_classes"]) or int(acc["dim"]) != int(into["dim"]):
+            raise ValueError("LdaEstimate::Read, dimension or classes count mismatch, %d, %d,  vs. %d, %d"
+                             % (into["num_classes"], into["dim"], acc["num_classes"], acc["dim"]))
+    else:
+        into.update(dim=int(acc["dim"]), num_classes=int(acc["num_classes"]))
+        for k in ("zero", "first", "second"):
+            into[k] = np.zeros_like(np.asarray(acc[k], np.float64))
+    for k in ("zero", "first", "second"):
+        into[k] += acc[k]
+    return into
+
+
+def read_lda_accs(s, binary=True, add_into=None):
+    """LdaEstimate::Read (lda-estimate.cc:180-235): the sections in any order, any of them absent (zeros) or repeated (the
+    last one read counts; under add each one adds), except that <SECOND_ACCS> is demangled from the FLOAT counts and rows
+    read before it, which therefore must precede it.  add_into: an accumulator the values read are added to (add = true)."""
+    s = _as_stream(s)
+    expect_token(s, binary, "<LDAACCS>")
+    expect_token(s, binary, "<VECSIZE>")
+    dim = read_int32(s, binary)
+    expect_token(s, binary, "<NUMCLASSES>")
+    nc = read_int32(s, binary)
+    if add_into is not None and (int(add_into["num_classes"]) != 0 or int(add_into["dim"]) != 0):
+        if nc != int(add_into["num_classes"]) or dim != int(add_into["dim"]):
+            raise ValueError("LdaEstimate::Read, dimension or classes count mismatch, %d, %d,  vs. %d, %d"
+                             % (add_into["num_classes"], add_into["dim"], nc, dim))
+    q = dim * (dim + 1) // 2
+    acc = dict(zero=np.zeros(nc, np.float64), first=np.zeros((nc, dim), np.float64), second=np.zeros(q, np.float64), dim=dim, num_classes=nc)
+    tmp_zero = tmp_first = None
+    tok = read_token(s, binary)
+    while tok != "</LDAACCS>":
+        if tok == "<ZERO_ACCS>":
+            tmp_zero = read_vector(s, binary).astype(np.float64)
+            if tmp_zero.shape != (nc,):
+                raise ValueError("LdaEstimate::Read: %d counts for %d classes" % (len(tmp_zero), nc))
+            acc["zero"] = tmp_zero.copy()
+        elif tok == "<FIRST_ACCS>":
+            tmp_first = read_matrix(s, binary).astype(np.float64)
+            if tmp_first.size == 0 and nc * dim == 0:          # an empty matrix is written as 0 x 0
+                tmp_first = np.zeros((nc, dim), np.float64)
+            if tmp_first.shape != (nc, dim):
+                raise ValueError("LdaEstimate::Read: first-order statistics of %d rows for %d classes" % (tmp_first.shape[0], nc))
+            acc["first"] = tmp_first.copy()
+        elif tok == "<SECOND_ACCS>":
+            M = read_sp_matrix(s, binary).astype(np.float64)
+            if M.shape[0] != dim:
+                raise ValueError("LdaEstimate::Read: second-order statistics of %d rows, the accumulator %d" % (M.shape[0], dim))
+            if tmp_zero is None or tmp_first is None:
+                raise ValueError("LdaEstimate::Read: <SECOND_ACCS> before the counts and rows it is demangled with")
+            r, c = np.tril_indices(dim)
+            acc["second"] = _lda_mangle(M[r, c], tmp_zero, tmp_first, 1.0)
+        else:
+            raise ValueError("Unexpected token '%s' in file " % tok)
+        tok = read_token(s, binary)
+    return acc if add_into is None else add_lda_accs(add_into, acc)

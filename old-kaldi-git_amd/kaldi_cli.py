@@ -698,6 +698,17 @@ def read_kaldi_object(rxfilename, reader):
         _close(f, kind)
 
 
+def write_kaldi_object(wxfilename, binary, write):
+    """`Output ko(wxfilename, binary); obj.Write(ko.Stream(), binary)`: the binary header, write(f), and the stream closed -
+    a pipe whose command fails is an error, as in Output's destructor."""
+    f, kind = open_output(wxfilename)
+    if binary:
+        f.write(b"\0B")
+    write(f)
+    if _close(f, kind) != 0:
+        raise KaldiError("Error closing output stream " + wxfilename)
+
+
 # ---------------------------------------------------------------- tables
 class SequentialTableReader:
     """SequentialTableReader<Holder> (kaldi-table-inl.h:63-520): iterate (key, object) of an rspecifier.  `kind` names the

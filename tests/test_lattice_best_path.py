@@ -227,7 +227,7 @@ def test_the_two_tools_through_a_real_pipe(tmp_path):
 
 
 def test_sweep_lists_and_substitution():
-    bp = __import__("tools.lattice_best_path", fromlist=["x"])
+    bp = pkg("kaldi_tool")
     assert bp.parse_sweep_list("9:20", "x") == [str(v) for v in range(9, 21)]
     assert bp.parse_sweep_list("0.0,0.5,1.0", "x") == ["0.0", "0.5", "1.0"]
     assert bp.substitute("ark,t:scoring/penalty_WIP/LMWT.tra", "12", "0.5") == "ark,t:scoring/penalty_0.5/12.tra"

@@ -302,7 +302,7 @@ def test_oracle_tool_refusals_and_beam_substitution(tmp_path, capfd, restated_de
     err = capfd.readouterr().err
     assert "--wildcard-symbols-list option deprecated." in err and "requires --word-symbol-table option" in err
     assert not list(tmp_path.glob("tra_*")) and not (tmp_path / "same").exists()
-    assert tool.beam_specs("ark:x_BEAM.tra", ["2", "4.5"]) == ["ark:x_2.tra", "ark:x_4.5.tra"]
+    assert tool.kt.beam_specs("ark:x_BEAM.tra", ["2", "4.5"]) == ["ark:x_2.tra", "ark:x_4.5.tra"]
     # the sweep: one file and one Overall line per beam; a wide beam gives the unpruned answer
     assert tool.main(["--acoustic-scale=0.5", "--beams=0.25,1000", rs, ref_rs, out]) == 0
     err = capfd.readouterr().err

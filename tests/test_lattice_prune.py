@@ -189,8 +189,8 @@ def test_tool_option_errors(tmp_path, capfd):
 
 def test_tool_scales_and_sweep_helpers():
     tool = _tool()
-    assert tool.parse_sweep_list("9:11", "x") == ["9", "10", "11"]
-    assert tool.substitute("ark:pruned/penalty_WIP/LMWT.lats", "12", "0.5") == "ark:pruned/penalty_0.5/12.lats"
+    assert tool.kt.parse_sweep_list("9:11", "x") == ["9", "10", "11"]
+    assert tool.kt.substitute("ark:pruned/penalty_WIP/LMWT.lats", "12", "0.5") == "ark:pruned/penalty_0.5/12.lats"
     ac = tool.plain_scale(1.0, 12.0)
     assert ac.dtype == np.float32 and ac == np.float32(1.0) / np.float32(12.0)
     assert tool.plain_scale(0.1, 1.0) == np.float32(0.1)

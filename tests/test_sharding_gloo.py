@@ -67,7 +67,9 @@ def _disc_worker(rank, world, port, q):
                  tot_num_objf=-7.0 * (rank + 1), tot_den_objf=-9.0 * (rank + 1))
     grads = [torch.full((5, 3), float(rank + 1)), torch.full((11,), 10.0 * (rank + 1)), torch.full((2, 2), -1.0)]
     out = sharding.reduce_discriminative(stats, grads, bucket_bytes=64)   # tiny buckets: several all-reduces
-    q.put((rank, out, [g.clone() for g in grads]))
+    # numpy copies, not tensors: a tensor goes through the queue as a descriptor the parent fetches from THIS process's
+    # listener, which is gone once the worker has exited (FileNotFoundError in the parent's q.get, now and then)
+    q.put((rank, out, [g.numpy().copy() for g in grads]))
     dist.destroy_process_group()
 
 
@@ -87,7 +89,8 @@ def test_discriminative_stats_and_gradients_over_gloo():
         assert out["tot_t"] == 300.0 and out["tot_t_weighted"] == 150.0 and out["tot_num_count"] == 7.0
         assert out["tot_num_objf"] == -21.0 and out["tot_den_objf"] == -27.0
         assert abs(out["objf_per_frame"] - (-21.0 + 27.0) / 150.0) < 1e-12
-        assert torch.all(grads[0] == 3.0) and torch.all(grads[1] == 30.0) and torch.all(grads[2] == -2.0)
+        assert [g.shape for g in grads] == [(5, 3), (11,), (2, 2)] and all(g.dtype == np.float32 for g in grads)
+        assert np.all(grads[0] == 3.0) and np.all(grads[1] == 30.0) and np.all(grads[2] == -2.0)
     # single process: identity
     out = sharding.reduce_discriminative(dict(tot_t=1, tot_t_weighted=1, tot_num_count=0, tot_num_objf=0, tot_den_objf=-2.0))
     assert out["tot_den_objf"] == -2.0 and out["objf_per_frame"] == -2.0

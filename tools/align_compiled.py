@@ -23,6 +23,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
 USAGE = {
     "gmm": ("Align features given [GMM-based] models.\n"
@@ -54,7 +55,7 @@ def register_options(po, kind):
     if kind == "nnet2":
         po.register("use-gpu", "yes", "yes|no|optional|wait, only has effect if compiled with CUDA")
     po.register("batch-frames", 200000, "[MI355X] frames per scoring pass / search call", int)
-    po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
+    kt.register_gpu(po)
     po.register("dry-run", False, "[MI355X] read the inputs, give the warnings about them, align nothing and write nothing into the "
                 "tables (a plumbing test without a GPU)")
 
@@ -66,27 +67,13 @@ def check_beams(cli, beam, retry_beam):
 
 
 def main(argv=None, kind="gmm"):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
     prog = "gmm-align-compiled" if kind == "gmm" else "nnet-align-compiled"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, kind, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:     # "catch(const std::exception &e) { std::cerr << e.what(); return -1; }"
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(prog, lambda cli, argv: run(cli, argv, kind, prog), argv, kt.KALDI_KH)
 
 
 def run(cli, argv, kind, prog):
-    cli.start_pipe_helper()               # before anything initialises the GPU
-    po = cli.ParseOptions(USAGE[kind])
-    register_options(po, kind)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() < 4 or po.num_args() > 5:
-        po.print_usage()
+    po = kt.parse(cli, prog, USAGE[kind], argv, lambda po: register_options(po, kind), range(4, 6))
+    if po is None:
         return 1
     model_rx, fst_rspec, feats_rspec, ali_wspec = (po.get_arg(i) for i in (1, 2, 3, 4))
     scores_wspec = po.get_opt_arg(5)
@@ -94,7 +81,7 @@ def run(cli, argv, kind, prog):
     if kind == "nnet2":
         tm, (comps, priors) = cli.read_kaldi_object(model_rx, lambda s, b: (kio.read_transition_model(s, b), kio.read_am_nnet(s, b)))
     else:
-        tm, am = cli.read_kaldi_object(model_rx, lambda s, b: (kio.read_transition_model(s, b), kio.read_am_diag_gmm(s, b)))
+        tm, am = kt.read_gmm_model(cli, kio, model_rx)
     fst_reader = cli.SequentialTableReader(fst_rspec, "fst")
     feature_reader = cli.RandomAccessTableReader(feats_rspec, "matrix")
     ali_w = cli.TableWriter(ali_wspec, "int32_vector")
@@ -110,14 +97,13 @@ def run(cli, argv, kind, prog):
         if state["score"] is not None:
             return
         import torch  # noqa: F401
-        api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
+        kt.select_gpu(api, po)
         if kind == "nnet2":
             nnet = api.Nnet(comps, priors)
             state["input_dim"] = nnet.input_dim()
             state["score"] = lambda feats, off: nnet.compute(feats, off, pad_input=True, epilogue=True, prob_scale=acwt)[0]   # DecodableAmNnet
         else:
-            gconsts, _ = api.gmm_compute_gconsts(am["weights"], am["means_invvars"], am["inv_vars"])
-            gmm = api.AmDiagGmm(gconsts, am["means_invvars"], am["inv_vars"], am["pdf_offsets"])
+            gmm = kt.device_gmm(api, am)
             state["input_dim"] = am["dim"]
 
             def score(feats, off):        # DecodableAmDiagGmmScaled::LogLikelihood (decodable-am-diag-gmm.h:142-145)
@@ -127,16 +113,14 @@ def run(cli, argv, kind, prog):
             state["score"] = score
 
     def flush(batch):
-        if not batch or dry:
+        if dry:
             return
-        import torch
         device()
         for utt, _, m in batch:
             if m.shape[1] != state["input_dim"]:
                 raise cli.KaldiError("feature dimension %d of %s does not match the model's input %d" % (m.shape[1], utt, state["input_dim"]))
         off = np.concatenate([[0], np.cumsum([len(m) for _, _, m in batch])]).astype(np.int32)
-        feats = torch.from_numpy(np.ascontiguousarray(np.concatenate([m for _, _, m in batch], 0), dtype=np.float32)).cuda()
-        loglikes = state["score"](feats, off)
+        loglikes = state["score"](kt.stack_rows([m for _, _, m in batch]), off)
         res = api.align_compiled([g for _, g, _ in batch], loglikes, off, tm["tid2pdf"], beam, retry_beam, careful=po["careful"])
         for (utt, _, m), r in zip(batch, res):
             report(utt, len(m), r)
@@ -160,31 +144,30 @@ def run(cli, argv, kind, prog):
         ali_w.write(utt, np.asarray(r["alignment"], np.int32))
         scores_w.write(utt, neg)
 
-    batch, frames, checked = [], 0, False
-    for utt, g in fst_reader:
-        if not feature_reader.has_key(utt):
-            tot["err"] += 1
-            cli.warn("No features for utterance " + utt)
-            continue
-        m = feature_reader.value(utt)
-        if m.shape[0] == 0:
-            cli.warn("Zero-length utterance: " + utt)
-            tot["err"] += 1
-            continue
-        g = api.add_transition_probs(g, tm, po["transition-scale"], po["self-loop-scale"])
-        if not checked:
-            check_beams(cli, beam, retry_beam)
-            checked = True
-        if int(g["num_states"]) == 0 or int(g["start"]) < 0:
-            cli.warn("Empty decoding graph for " + utt, WHERE)
-            tot["err"] += 1
-            continue
-        batch.append((utt, g, m))
-        frames += m.shape[0]
-        if frames >= po["batch-frames"]:
-            flush(batch)
-            batch, frames = [], 0
-    flush(batch)
+    def utterances():
+        checked = False
+        for utt, g in fst_reader:
+            if not feature_reader.has_key(utt):
+                tot["err"] += 1
+                cli.warn("No features for utterance " + utt)
+                continue
+            m = feature_reader.value(utt)
+            if m.shape[0] == 0:
+                cli.warn("Zero-length utterance: " + utt)
+                tot["err"] += 1
+                continue
+            g = api.add_transition_probs(g, tm, po["transition-scale"], po["self-loop-scale"])
+            if not checked:
+                check_beams(cli, beam, retry_beam)
+                checked = True
+            if int(g["num_states"]) == 0 or int(g["start"]) < 0:
+                cli.warn("Empty decoding graph for " + utt, WHERE)
+                tot["err"] += 1
+                continue
+            yield utt, g, m
+
+    for batch in kt.batches(utterances(), lambda b: b[2].shape[0], po["batch-frames"], "after"):
+        flush(batch)
     ok = ali_w.close()
     scores_w.close()
     per_frame = tot["like"] / tot["frames"] if tot["frames"] else float("nan")

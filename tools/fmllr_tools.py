@@ -27,6 +27,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
 USAGE = {
     "ali-to-post": ("Convert alignments to posteriors\n"
@@ -70,43 +71,16 @@ USAGE = {
 }
 
 
-def _mods():
-    m = lambda n: importlib.import_module("old-kaldi-git_amd." + n)
-    return m("kaldi_cli"), m("kaldi_io")
-
-
 def main(argv=None, prog="gmm-est-fmllr"):
-    cli, _ = _mods()
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return RUN[prog](cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:     # "catch(const std::exception &e) { std::cerr << e.what(); return -1; }"
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
-
-
-def _options(cli, argv, prog, n_args, register=None):
-    cli.start_pipe_helper()               # before anything initialises the GPU
-    po = cli.ParseOptions(USAGE[prog])
-    if register:
-        register(po)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != n_args:
-        po.print_usage()
-        return None
-    return po
-
-
-def _select_gpu(api, po):
-    api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
+    return kt.run_tool(prog, lambda cli, argv: RUN[prog](cli, argv, prog), argv, kt.KALDI_KH)
 
 
 def _api():
     return importlib.import_module("old-kaldi-git_amd.api")
+
+
+def _kio():
+    return importlib.import_module("old-kaldi-git_amd.kaldi_io")
 
 
 def _is_rspecifier(cli, s):
@@ -120,7 +94,7 @@ def _read_token_map(cli, rspecifier):
 
 # ---------------------------------------------------------------- ali-to-post
 def run_ali_to_post(cli, argv, prog):
-    po = _options(cli, argv, prog, 2)
+    po = kt.parse(cli, prog, USAGE[prog], argv, None, 2)
     if po is None:
         return 1
     reader = cli.SequentialTableReader(po.get_arg(1), "int32_vector")
@@ -136,12 +110,12 @@ def run_ali_to_post(cli, argv, prog):
 
 # ---------------------------------------------------------------- weight-silence-post
 def run_weight_silence_post(cli, argv, prog):
-    po = _options(cli, argv, prog, 5, lambda po: po.register(
+    po = kt.parse(cli, prog, USAGE[prog], argv, lambda po: po.register(
         "distribute", False, "If true, rather than weighting the individual posteriors, apply the weighting to the whole frame: "
-        "i.e. on time t, scale all posterior entries by p(sil)*silence-weight + p(non-sil)*1.0"))
+        "i.e. on time t, scale all posterior entries by p(sil)*silence-weight + p(non-sil)*1.0"), 5)
     if po is None:
         return 1
-    _, kio = _mods()
+    kio = _kio()
     try:
         weight = float(po.get_arg(1))
     except ValueError:
@@ -165,36 +139,19 @@ def run_weight_silence_post(cli, argv, prog):
     return 0 if n != 0 else 1
 
 
-# ---------------------------------------------------------------- the model on the device
-def _read_model(cli, kio, rx):
-    return cli.read_kaldi_object(rx, lambda s, b: (kio.read_transition_model(s, b), kio.read_am_diag_gmm(s, b)))
-
-
-def _device_gmm(api, am):
-    gconsts, _ = api.gmm_compute_gconsts(am["weights"], am["means_invvars"], am["inv_vars"])
-    return api.AmDiagGmm(gconsts, am["means_invvars"], am["inv_vars"], am["pdf_offsets"])
-
-
-def _stack(mats, dim):
-    import torch
-    feats = np.ascontiguousarray(np.concatenate(mats, 0), dtype=np.float32) if mats else np.zeros((0, dim), np.float32)
-    return torch.from_numpy(feats).cuda()
-
-
 # ---------------------------------------------------------------- gmm-post-to-gpost
 def run_gmm_post_to_gpost(cli, argv, prog):
     def register(po):
         po.register("binary", True, "Write output in binary mode")
         po.register("rand-prune", 0.0, "Randomized pruning of posteriors less than this [MI355X: only 0 is supported]", float)
         po.register("batch-frames", 200000, "[MI355X] frames per library call", int)
-        po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
-    po = _options(cli, argv, prog, 4, register)
+        kt.register_gpu(po)
+    po = kt.parse(cli, prog, USAGE[prog], argv, register, 4)
     if po is None:
         return 1
     if po["rand-prune"] > 0.0:
         raise cli.KaldiError("--rand-prune=%g: RandPrune's random stream is not reproduced here; only --rand-prune=0 is supported" % po["rand-prune"])
-    _, kio = _mods()
-    tm, am = _read_model(cli, kio, po.get_arg(1))
+    tm, am = kt.read_gmm_model(cli, _kio(), po.get_arg(1))
     feature_reader = cli.SequentialTableReader(po.get_arg(2), "matrix")
     post_reader = cli.RandomAccessTableReader(po.get_arg(3), "posterior")
     writer = cli.TableWriter(po.get_arg(4), "gauss_post")
@@ -203,13 +160,11 @@ def run_gmm_post_to_gpost(cli, argv, prog):
     state = {}
 
     def flush(batch):
-        if not batch:
-            return
         if "gmm" not in state:
-            _select_gpu(api, po)
-            state["gmm"] = _device_gmm(api, am)
+            kt.select_gpu(api, po)
+            state["gmm"] = kt.device_gmm(api, am)
         posts = [fr for _, _, p in batch for fr in p]
-        gposts, like, weight = api.gmm_post_to_gpost(state["gmm"], _stack([m for _, m, _ in batch], am["dim"]), posts)
+        gposts, like, weight = api.gmm_post_to_gpost(state["gmm"], kt.stack_rows([m for _, m, _ in batch]), posts)
         feo = np.concatenate([[0], np.cumsum([len(fr) for fr in posts])])
         t0 = 0
         for key, m, p in batch:
@@ -223,28 +178,26 @@ def run_gmm_post_to_gpost(cli, argv, prog):
             writer.write(key, gposts[t0:t0 + len(p)])
             t0 += len(p)
 
-    batch, frames = [], 0
-    for key, mat in feature_reader:
-        if not post_reader.has_key(key):
-            tot["no_post"] += 1
-            continue
-        post = post_reader.value(key)
-        if len(post) != mat.shape[0]:
-            cli.warn("Posterior vector has wrong size %d vs. %d" % (len(post), mat.shape[0]))
-            tot["err"] += 1
-            continue
-        tot["done"] += 1
-        if mat.shape[0] == 0:
-            writer.write(key, [])
-            continue
-        if mat.shape[1] != am["dim"]:
-            raise cli.KaldiError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (mat.shape[1], am["dim"]))
-        batch.append((key, mat, api.convert_posterior_to_pdfs(tm["tid2pdf"], post)))
-        frames += mat.shape[0]
-        if frames >= po["batch-frames"]:
-            flush(batch)
-            batch, frames = [], 0
-    flush(batch)
+    def utterances():
+        for key, mat in feature_reader:
+            if not post_reader.has_key(key):
+                tot["no_post"] += 1
+                continue
+            post = post_reader.value(key)
+            if len(post) != mat.shape[0]:
+                cli.warn("Posterior vector has wrong size %d vs. %d" % (len(post), mat.shape[0]))
+                tot["err"] += 1
+                continue
+            tot["done"] += 1
+            if mat.shape[0] == 0:
+                writer.write(key, [])
+                continue
+            if mat.shape[1] != am["dim"]:
+                raise cli.KaldiError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (mat.shape[1], am["dim"]))
+            yield key, mat, api.convert_posterior_to_pdfs(tm["tid2pdf"], post)
+
+    for batch in kt.batches(utterances(), lambda b: b[1].shape[0], po["batch-frames"], "after"):
+        flush(batch)
     writer.close()
     cli.log("Done %d files, %d with no posteriors, %d with other errors." % (tot["done"], tot["no_post"], tot["err"]))
     cli.log("Overall avg like per frame (Gaussian only) = %g over %g frames." % (tot["like"] / tot["t"] if tot["t"] else float("nan"), tot["t"]))
@@ -262,12 +215,11 @@ def run_est_fmllr(cli, argv, prog):
         po.register("fmllr-update-type", "full", 'Update type for fMLLR ("full"|"diag"|"offset"|"none")')
         po.register("fmllr-min-count", 500.0, "Minimum count required to update fMLLR", float)
         po.register("fmllr-num-iters", 40, "Number of iterations in fMLLR update phase.", int)
-        po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
-    po = _options(cli, argv, prog, 4, register)
+        kt.register_gpu(po)
+    po = kt.parse(cli, prog, USAGE[prog], argv, register, 4)
     if po is None:
         return 1
-    _, kio = _mods()
-    tm, am = _read_model(cli, kio, po.get_arg(1))
+    tm, am = kt.read_gmm_model(cli, _kio(), po.get_arg(1))
     post_reader = cli.RandomAccessTableReader(po.get_arg(3), "gauss_post" if gpost else "posterior")
     writer = cli.TableWriter(po.get_arg(4), "matrix")
     api = _api()
@@ -324,11 +276,11 @@ def run_est_fmllr(cli, argv, prog):
     W = np.tile(np.eye(D, D + 1, dtype=np.float32), (S, 1, 1))
     impr, count, beta = np.zeros(S, np.float32), np.zeros(S, np.float32), np.zeros(S, np.float64)
     if mats:
-        _select_gpu(api, po)
-        gmm = _device_gmm(api, am)
+        kt.select_gpu(api, po)
+        gmm = kt.device_gmm(api, am)
         utt_rows = np.concatenate([[0], np.cumsum([len(m) for m in mats])]).astype(np.int32)
         kw = dict(gposts=posts) if gpost else dict(posts=posts, tid2pdf=tm["tid2pdf"])
-        W, impr, count, stats = api.estimate_fmllr(gmm, _stack(mats, D), utt_rows, np.asarray(spk_utts, np.int32), opts=opts, return_stats=True, **kw)
+        W, impr, count, stats = api.estimate_fmllr(gmm, kt.stack_rows(mats), utt_rows, np.asarray(spk_utts, np.int32), opts=opts, return_stats=True, **kw)
         beta = stats["beta"]
         t = api.fmllr_last_timings()
         cli.vlog(1, "component posteriors %.3f ms, frame stats %.3f ms, accumulate %.3f ms, update %.3f ms" % (
@@ -358,10 +310,10 @@ def run_compose_transforms(cli, argv, prog):
         po.register("utt2spk", "", "rspecifier for utterance to speaker map (if mixing utterance and speaker ids)")
         po.register("b-is-affine", False, "If true, treat last column of transform b as an offset term (only relevant if a is affine)")
         po.register("binary", True, "Write in binary mode (only relevant if output is a wxfilename)")
-    po = _options(cli, argv, prog, 3, register)
+    po = kt.parse(cli, prog, USAGE[prog], argv, register, 3)
     if po is None:
         return 1
-    _, kio = _mods()
+    kio = _kio()
     api = _api()
     a_fn, b_fn, c_fn = po.get_arg(1), po.get_arg(2), po.get_arg(3)
     a_rs, b_rs = _is_rspecifier(cli, a_fn), _is_rspecifier(cli, b_fn)
@@ -390,11 +342,7 @@ def run_compose_transforms(cli, argv, prog):
         c = compose(a, b)
         if c is None:
             return 1
-        f, kind = cli.open_output(c_fn)
-        if po["binary"]:
-            f.write(b"\0B")
-        kio.write_matrix(f, c, po["binary"])
-        f.close()
+        cli.write_kaldi_object(c_fn, po["binary"], lambda f: kio.write_matrix(f, c, po["binary"]))
         return 0
     writer = cli.TableWriter(c_fn, "matrix")
     if a_rs and b_rs:
@@ -434,11 +382,11 @@ def run_transform_feats(cli, argv, prog):
     def register(po):
         po.register("utt2spk", "", "rspecifier for utterance to speaker map")
         po.register("batch-frames", 200000, "[MI355X] frames per device pass", int)
-        po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
-    po = _options(cli, argv, prog, 3, register)
+        kt.register_gpu(po)
+    po = kt.parse(cli, prog, USAGE[prog], argv, register, 3)
     if po is None:
         return 1
-    _, kio = _mods()
+    kio = _kio()
     api = _api()
     t_fn = po.get_arg(1)
     glob = None
@@ -481,14 +429,14 @@ def run_transform_feats(cli, argv, prog):
             return
         import torch
         if "gpu" not in state:
-            _select_gpu(api, po)
+            kt.select_gpu(api, po)
             state["gpu"] = True
         out = {}
         groups = {}
         for i, (utt, feat, tr) in enumerate(batch):
             groups.setdefault(id(tr), (tr, []))[1].append(i)
         for tr, idx in groups.values():
-            x = torch.from_numpy(np.ascontiguousarray(np.concatenate([batch[i][1] for i in idx], 0), dtype=np.float32)).cuda()
+            x = kt.stack_rows([batch[i][1] for i in idx])
             y = api.transform_feats(torch.from_numpy(np.ascontiguousarray(tr, dtype=np.float32)).cuda(), x).cpu().numpy()
             r = 0
             for i in idx:

@@ -30,6 +30,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
 PROG = "gmm-acc-mllt"
 USAGE = ("Accumulate MLLT (global STC) statistics\n"
@@ -39,53 +40,25 @@ USAGE = ("Accumulate MLLT (global STC) statistics\n"
 BATCH_FRAMES = 200000
 
 
-def _g(x):
-    return "%g" % x
-
-
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [PROG] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:     # "catch(const std::exception &e) { std::cerr << e.what(); return -1; }"
-        sys.stderr.write("ERROR (%s) %s\n" % (PROG, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH)
 
 
 def run(cli, argv):
-    cli.start_pipe_helper()               # before anything initialises the GPU
-    sharding = importlib.import_module("old-kaldi-git_amd.sharding")
-    po = cli.ParseOptions(USAGE)
-    po.register("binary", True, "Write output in binary mode")
-    po.register("rand-prune", 0.25, "Randomized pruning parameter to speed up accumulation (larger -> more pruning.  May exceed one).", float)
-    po.register("batch-frames", BATCH_FRAMES, "[MI355X] stacked rows per library pass", int)
-    po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
-    po.register("world", 0, "[MI355X] number of ranks sharing the job (default: WORLD_SIZE, else 1).  Rank r is the recipe's JOB r + 1: "
-                "every JOB in the arguments becomes r + 1 (run.pl JOB=1:$nj)", int)
-    po.register("rank", -1, "[MI355X] this process's rank (default: RANK, else 0)", int)
-    w_opt = r_opt = None
-    for a in argv[1:]:
-        if a.startswith("--world="):
-            w_opt = int(a.split("=", 1)[1])
-        elif a.startswith("--rank="):
-            r_opt = int(a.split("=", 1)[1])
-    rank, world = sharding.tool_ranks(w_opt or 0, -1 if r_opt is None else r_opt)
-    raw_pos = [a for a in argv[1:] if not a.startswith("--")]
-    if world > 1:
-        argv = [argv[0]] + sharding.job_substitute(argv[1:], rank)
-    po.read(argv)
-    cli.set_program_name(PROG)
-    if po.num_args() != 4:
-        po.print_usage()
+    def register(po):
+        po.register("binary", True, "Write output in binary mode")
+        po.register("rand-prune", 0.25, "Randomized pruning parameter to speed up accumulation (larger -> more pruning.  May exceed one).", float)
+        po.register("batch-frames", BATCH_FRAMES, "[MI355X] stacked rows per library pass", int)
+        kt.register_gpu(po)
+        kt.register_ranks(po)
+    argv, rank, world, raw_pos = kt.rank_substitute(argv)
+    po = kt.parse(cli, PROG, USAGE, argv, register, 4)
+    if po is None:
         return 1
     if world > 1 and "JOB" not in raw_pos[3]:
         raise cli.KaldiError("--world=%d: the statistics file needs JOB in its name ($x.JOB.macc), or the ranks overwrite each other" % world)
     kio = importlib.import_module("old-kaldi-git_amd.kaldi_io")
-    tm, am = cli.read_kaldi_object(po.get_arg(1), lambda s, b: (kio.read_transition_model(s, b), kio.read_am_diag_gmm(s, b)))
+    tm, am = kt.read_gmm_model(cli, kio, po.get_arg(1))
     api = importlib.import_module("old-kaldi-git_amd.api")
     rand_prune = np.float32(po["rand-prune"])                            # BaseFloat rand_prune
     if not rand_prune >= 0:
@@ -100,14 +73,10 @@ def run(cli, argv):
 
     def flush(batch):
         """One library pass over the batch's stacked rows, added into the running accumulator; then the per-file figures."""
-        if not batch:
-            return
-        import torch
         if "gmm" not in state:
-            api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
-            gconsts, _ = api.gmm_compute_gconsts(am["weights"], am["means_invvars"], am["inv_vars"])
-            state["gmm"] = api.AmDiagGmm(gconsts, am["means_invvars"], am["inv_vars"], am["pdf_offsets"])
-        x = torch.from_numpy(np.ascontiguousarray(np.concatenate([b["mat"] for b in batch], 0), dtype=np.float32)).cuda()
+            kt.select_gpu(api, po)
+            state["gmm"] = kt.device_gmm(api, am)
+        x = kt.stack_rows([b["mat"] for b in batch])
         pdf_posts = [fr for b in batch for fr in b["pdf_post"]]
         state["acc"], ent, like = api.accumulate_mllt_stats(state["gmm"], x, pdf_posts, rand_prune=float(rand_prune), seed=1, into=state["acc"],
                                                             return_entries=True,
@@ -116,61 +85,41 @@ def run(cli, argv):
         lw = (like * w).astype(np.float32)                                # AccumulateFromGmm(...) * weight, BaseFloat
         cli.vlog(1, "batch of %d rows / %d entries in %d utterances, %d draws so far" % (x.shape[0], len(w), len(batch), state["acc"]["draws"]))
         t0 = 0
-        f32sum = lambda a: float(np.cumsum(a, dtype=np.float32)[-1]) if len(a) else 0.0     # BaseFloat += BaseFloat, in order
         for b in batch:
             e0, e1 = int(ent["feo"][t0]), int(ent["feo"][t0 + len(b["pdf_post"])])
             t0 += len(b["pdf_post"])
-            like_file, w_file = f32sum(lw[e0:e1]), f32sum(w[e0:e1])
-            with np.errstate(invalid="ignore", divide="ignore"):
-                avg = np.float32(like_file) / np.float32(w_file)
-            cli.log("Average like for this file is %s over %s frames." % (_g(avg), _g(w_file)))
-            tot["like"] += like_file
-            tot["t"] += w_file
-            if b["index"] % 10 == 0:
-                cli.log("Avg like per frame so far is " + _g(tot["like"] / tot["t"] if tot["t"] else float("nan")))
+            kt.report_file_like(cli, tot, kt.f32sum(lw[e0:e1]), kt.f32sum(w[e0:e1]), b["index"])
 
-    batch, frames = [], 0
-    for key, mat in feature_reader:
-        if not post_reader.has_key(key):
-            n["no_post"] += 1
-            continue
-        post = post_reader.value(key)
-        if len(post) != mat.shape[0]:
-            cli.warn("Posterior vector has wrong size %d vs. %d" % (len(post), mat.shape[0]))
-            n["err"] += 1
-            continue
-        n["done"] += 1
-        if mat.shape[0] == 0:
-            cli.log("Average like for this file is %s over %s frames." % (_g(float("nan")), _g(0.0)))
-            continue
-        if mat.shape[1] != am["dim"]:
-            raise cli.KaldiError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (mat.shape[1], am["dim"]))
-        tids = np.asarray([t for fr in post for t, _ in fr], np.int64)
-        if len(tids) and (tids.min() < 1 or tids.max() > n_tids):
-            raise cli.KaldiError("utterance %s: transition-id %d, the model has 1 .. %d" % (
-                key, int(tids.max() if tids.min() >= 1 else tids.min()), n_tids))
-        pdf_post = api.convert_posterior_to_pdfs(tid2pdf, post)
-        if batch and frames + mat.shape[0] > po["batch-frames"]:         # this utterance would take the batch over: it starts the next
-            flush(batch)
-            batch, frames = [], 0
-        batch.append(dict(key=key, mat=mat, pdf_post=pdf_post, index=n["done"]))
-        frames += mat.shape[0]
-    flush(batch)
+    def utterances():
+        for key, mat in feature_reader:
+            if not post_reader.has_key(key):
+                n["no_post"] += 1
+                continue
+            post = post_reader.value(key)
+            if len(post) != mat.shape[0]:
+                cli.warn("Posterior vector has wrong size %d vs. %d" % (len(post), mat.shape[0]))
+                n["err"] += 1
+                continue
+            n["done"] += 1
+            if mat.shape[0] == 0:
+                cli.log("Average like for this file is %s over %s frames." % (kt.g(float("nan")), kt.g(0.0)))
+                continue
+            if mat.shape[1] != am["dim"]:
+                raise cli.KaldiError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (mat.shape[1], am["dim"]))
+            kt.check_transition_ids(cli, key, np.asarray([t for fr in post for t, _ in fr], np.int64), n_tids)
+            yield dict(key=key, mat=mat, pdf_post=api.convert_posterior_to_pdfs(tid2pdf, post), index=n["done"])
+
+    for batch in kt.batches(utterances(), lambda b: b["mat"].shape[0], po["batch-frames"], "before"):
+        flush(batch)
     cli.log("Done %d files, %d with no posteriors, %d with other errors." % (n["done"], n["no_post"], n["err"]))
     cli.log("Overall avg like per frame (Gaussian only) = %s over %s frames." % (
-        _g(tot["like"] / tot["t"] if tot["t"] else float("nan")), _g(tot["t"])))
+        kt.g(tot["like"] / tot["t"] if tot["t"] else float("nan")), kt.g(tot["t"])))
     acc = state["acc"]
     if acc is None:                       # nothing accumulated: the zero accumulators of MlltAccs::Init
         dim = int(am["dim"])
         acc = dict(beta=0.0, G=np.zeros((dim, dim * (dim + 1) // 2)), dim=dim)
-    f, kind = cli.open_output(po.get_arg(4))          # WriteKaldiObject(mllt_accs, accs_wxfilename, binary)
-    if po["binary"]:
-        f.write(b"\0B")
-    kio.write_mllt_accs(f, acc, po["binary"])
-    if kind == "stdout":
-        f.flush()
-    elif f.close() not in (None, 0):
-        raise cli.KaldiError("Error closing output stream " + po.get_arg(4))
+    # WriteKaldiObject(mllt_accs, accs_wxfilename, binary)
+    cli.write_kaldi_object(po.get_arg(4), po["binary"], lambda f: kio.write_mllt_accs(f, acc, po["binary"]))
     cli.log("Written accs.")
     return 0 if n["done"] != 0 else 1
 

@@ -31,6 +31,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
 USAGE = {
     "gmm-acc-stats-ali": ("Accumulate stats for GMM training.\n"
@@ -54,50 +55,8 @@ USAGE = {
 BATCH_FRAMES = 200000
 
 
-def _mods():
-    m = lambda n: importlib.import_module("old-kaldi-git_amd." + n)
-    return m("kaldi_cli"), m("kaldi_io")
-
-
 def main(argv=None, prog="gmm-acc-stats-ali"):
-    cli, _ = _mods()
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return RUN[prog](cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:     # "catch(const std::exception &e) { std::cerr << e.what(); return -1; }"
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
-
-
-def _options(cli, argv, prog, ok_args, register):
-    cli.start_pipe_helper()               # before anything initialises the GPU
-    po = cli.ParseOptions(USAGE[prog])
-    register(po)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if not ok_args(po.num_args()):
-        po.print_usage()
-        return None
-    return po
-
-
-def _write_accs(cli, kio, wxfilename, acc, binary):
-    """Output ko(accs_wxfilename, binary); transition_accs.Write; gmm_accs.Write."""
-    f, kind = cli.open_output(wxfilename)
-    if binary:
-        f.write(b"\0B")
-    kio.write_gmm_accs(f, acc, binary)
-    if kind == "stdout":
-        f.flush()
-    elif f.close() not in (None, 0):
-        raise cli.KaldiError("Error closing output stream " + wxfilename)
-
-
-def _g(x):
-    return "%g" % x
+    return kt.run_tool(prog, lambda cli, argv: RUN[prog](cli, argv, prog), argv, kt.KALDI_KH)
 
 
 # ---------------------------------------------------------------- gmm-acc-stats-ali, gmm-acc-stats, gmm-acc-stats-twofeats
@@ -109,12 +68,12 @@ def run_acc_stats(cli, argv, prog):
         if prog == "gmm-acc-stats":
             po.register("update-flags", "mvwt", "Which GMM parameters will be updated: subset of mvwt.")
         po.register("batch-frames", BATCH_FRAMES, "[MI355X] stacked rows per library pass", int)
-        po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
-    po = _options(cli, argv, prog, lambda n: n == (5 if two else 4), register)
+        kt.register_gpu(po)
+    po = kt.parse(cli, prog, USAGE[prog], argv, register, 5 if two else 4)
     if po is None:
         return 1
-    _, kio = _mods()
-    tm, am = cli.read_kaldi_object(po.get_arg(1), lambda s, b: (kio.read_transition_model(s, b), kio.read_am_diag_gmm(s, b)))
+    kio = importlib.import_module("old-kaldi-git_amd.kaldi_io")
+    tm, am = kt.read_gmm_model(cli, kio, po.get_arg(1))
     api = importlib.import_module("old-kaldi-git_amd.api")
     flags = api.gmm_flags(po["update-flags"] if prog == "gmm-acc-stats" else api.kGmmAll)
     tid2pdf = tm["tid2pdf"]
@@ -124,27 +83,17 @@ def run_acc_stats(cli, argv, prog):
     post_reader = cli.RandomAccessTableReader(po.get_arg(4 if two else 3), "int32_vector" if ali else "posterior")
     n = dict(done=0, err=0, no2nd=0, no_post=0)
     tot = dict(like=0.0, t=0 if ali else 0.0)
-    state = dict(acc=None, trans=np.zeros(n_tids + 1, np.float64))       # trans_model.InitStats
-
-    def check_tids(key, tids):
-        if len(tids) and (tids.min() < 1 or tids.max() > n_tids):
-            raise cli.KaldiError("utterance %s: transition-id %d, the model has 1 .. %d" % (
-                key, int(tids.max() if tids.min() >= 1 else tids.min()), n_tids))
+    state = dict(acc=None, new_dim=0, trans=np.zeros(n_tids + 1, np.float64))       # trans_model.InitStats
 
     def flush(batch):
         """One library pass over the batch's stacked rows, added into the running accumulator; then the per-file figures."""
-        if not batch:
-            return
-        import torch
         if "gmm" not in state:
-            api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
-            gconsts, _ = api.gmm_compute_gconsts(am["weights"], am["means_invvars"], am["inv_vars"])
-            state["gmm"] = api.AmDiagGmm(gconsts, am["means_invvars"], am["inv_vars"], am["pdf_offsets"])
-        stack = lambda mats: torch.from_numpy(np.ascontiguousarray(np.concatenate(mats, 0), dtype=np.float32)).cuda()
+            kt.select_gpu(api, po)
+            state["gmm"] = kt.device_gmm(api, am)
         pdf_posts = [fr for b in batch for fr in b["pdf_post"]]
-        x1 = stack([b["mat"] for b in batch])
+        x1 = kt.stack_rows([b["mat"] for b in batch])
         state["acc"], ent, like = api.accumulate_gmm_stats(state["gmm"], x1, pdf_posts=pdf_posts, flags=flags, into=state["acc"],
-                                                           stats_feats=stack([b["mat2"] for b in batch]) if two else None,
+                                                           stats_feats=kt.stack_rows([b["mat2"] for b in batch]) if two else None,
                                                            return_entries=True)
         w = ent["weight"]
         lw = (like * w).astype(np.float32)                                      # log_like * weight, BaseFloat
@@ -155,82 +104,78 @@ def run_acc_stats(cli, argv, prog):
         for b in batch:
             e0, e1 = int(ent["feo"][t0]), int(ent["feo"][t0 + len(b["pdf_post"])])
             t0 += len(b["pdf_post"])
-            f32sum = lambda a: float(np.cumsum(a, dtype=np.float32)[-1]) if len(a) else 0.0     # BaseFloat += BaseFloat, in order
-            like_file = f32sum(like[e0:e1] if ali else lw[e0:e1])
-            w_file = len(b["pdf_post"]) if ali else f32sum(w[e0:e1])
+            like_file = kt.f32sum(like[e0:e1] if ali else lw[e0:e1])
+            w_file = len(b["pdf_post"]) if ali else kt.f32sum(w[e0:e1])
             np.add.at(state["trans"], b["tids"], b["tid_w"].astype(np.float64))                 # (*stats)(tid) += prob, in order
+            if two:
+                kt.report_file_like(cli, tot, like_file, w_file, b["index"])
+                continue
             tot["like"] += like_file
             tot["t"] += w_file
-            with np.errstate(invalid="ignore", divide="ignore"):
-                avg = np.float32(like_file) / np.float32(w_file)
-            if two:
-                cli.log("Average like for this file is %s over %s frames." % (_g(avg), _g(w_file)))
-                if b["index"] % 10 == 0:
-                    cli.log("Avg like per frame so far is " + _g(tot["like"] / tot["t"] if tot["t"] else float("nan")))
-            elif b["index"] % 50 == 0:
-                cli.log("Processed %d utterances; for utterance %s avg. like is %s over %s frames." % (b["index"], b["key"], _g(avg), _g(w_file)))
+            if b["index"] % 50 == 0:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    avg = np.float32(like_file) / np.float32(w_file)
+                cli.log("Processed %d utterances; for utterance %s avg. like is %s over %s frames." % (b["index"], b["key"], kt.g(avg), kt.g(w_file)))
 
-    batch, frames = [], 0
-    new_dim = 0
-    for key, mat in feature_reader:
-        if two and not feature2_reader.has_key(key):
-            cli.warn("For utterance %s, second features not present." % key)
-            n["no2nd"] += 1
-            continue
-        if not post_reader.has_key(key):
+    def utterances():
+        for key, mat in feature_reader:
+            if two and not feature2_reader.has_key(key):
+                cli.warn("For utterance %s, second features not present." % key)
+                n["no2nd"] += 1
+                continue
+            if not post_reader.has_key(key):
+                if ali:
+                    cli.warn("No alignment for utterance " + key)
+                    n["err"] += 1
+                elif two:
+                    n["no_post"] += 1
+                else:
+                    cli.warn("Could not find posteriors for utterance " + key)
+                    n["err"] += 1
+                continue
+            post = post_reader.value(key)
+            mat2 = feature2_reader.value(key) if two else None
+            if len(post) != mat.shape[0]:
+                cli.warn(("Alignments has wrong size %d vs. %d" if ali else "Posteriors has wrong size %d vs. %d" if two
+                          else "Posterior vector has wrong size %d vs. %d") % (len(post), mat.shape[0]))
+                n["err"] += 1
+                continue
+            if two and mat2.shape[0] != mat.shape[0]:
+                cli.warn("Features have mismatched numbers of frames %d vs. %d" % (mat.shape[0], mat2.shape[0]))
+                n["err"] += 1
+                continue
+            n["done"] += 1
+            if mat.shape[0] == 0:
+                continue
+            if mat.shape[1] != am["dim"]:
+                raise cli.KaldiError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (mat.shape[1], am["dim"]))
+            if two:
+                if state["new_dim"] == 0:
+                    state["new_dim"] = mat2.shape[1]
+                elif mat2.shape[1] != state["new_dim"]:
+                    raise cli.KaldiError("second features of %s have dimension %d, the accumulators %d" % (key, mat2.shape[1], state["new_dim"]))
             if ali:
-                cli.warn("No alignment for utterance " + key)
-                n["err"] += 1
-            elif two:
-                n["no_post"] += 1
+                tids = np.asarray(post, np.int64).reshape(-1)
+                kt.check_transition_ids(cli, key, tids, n_tids)
+                tid_w = np.ones(len(tids), np.float32)
+                pdf_post = [[(int(p), 1.0)] for p in tid2pdf[tids]]
             else:
-                cli.warn("Could not find posteriors for utterance " + key)
-                n["err"] += 1
-            continue
-        post = post_reader.value(key)
-        mat2 = feature2_reader.value(key) if two else None
-        if len(post) != mat.shape[0]:
-            cli.warn(("Alignments has wrong size %d vs. %d" if ali else "Posteriors has wrong size %d vs. %d" if two
-                      else "Posterior vector has wrong size %d vs. %d") % (len(post), mat.shape[0]))
-            n["err"] += 1
-            continue
-        if two and mat2.shape[0] != mat.shape[0]:
-            cli.warn("Features have mismatched numbers of frames %d vs. %d" % (mat.shape[0], mat2.shape[0]))
-            n["err"] += 1
-            continue
-        n["done"] += 1
-        if mat.shape[0] == 0:
-            continue
-        if mat.shape[1] != am["dim"]:
-            raise cli.KaldiError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (mat.shape[1], am["dim"]))
-        if two:
-            if new_dim == 0:
-                new_dim = mat2.shape[1]
-            elif mat2.shape[1] != new_dim:
-                raise cli.KaldiError("second features of %s have dimension %d, the accumulators %d" % (key, mat2.shape[1], new_dim))
-        if ali:
-            tids = np.asarray(post, np.int64).reshape(-1)
-            check_tids(key, tids)
-            tid_w = np.ones(len(tids), np.float32)
-            pdf_post = [[(int(p), 1.0)] for p in tid2pdf[tids]]
-        else:
-            tids = np.asarray([t for fr in post for t, _ in fr], np.int64)
-            check_tids(key, tids)
-            tid_w = np.asarray([x for fr in post for _, x in fr], np.float32)
-            pdf_post = api.convert_posterior_to_pdfs(tid2pdf, post)
-        if batch and frames + mat.shape[0] > po["batch-frames"]:         # this utterance would take the batch over: it starts the next
-            flush(batch)
-            batch, frames = [], 0
-        batch.append(dict(key=key, mat=mat, mat2=mat2, pdf_post=pdf_post, tids=tids, tid_w=tid_w, index=n["done"]))
-        frames += mat.shape[0]
-    flush(batch)
+                tids = np.asarray([t for fr in post for t, _ in fr], np.int64)
+                kt.check_transition_ids(cli, key, tids, n_tids)
+                tid_w = np.asarray([x for fr in post for _, x in fr], np.float32)
+                pdf_post = api.convert_posterior_to_pdfs(tid2pdf, post)
+            yield dict(key=key, mat=mat, mat2=mat2, pdf_post=pdf_post, tids=tids, tid_w=tid_w, index=n["done"])
+
+    for batch in kt.batches(utterances(), lambda b: b["mat"].shape[0], po["batch-frames"], "before"):
+        flush(batch)
+    new_dim = state["new_dim"]
     if two:
         cli.log("Done %d files, %d with no posteriors, %d with no second features, %d with other errors." % (
             n["done"], n["no_post"], n["no2nd"], n["err"]))
     else:
         cli.log("Done %d files, %d with errors." % (n["done"], n["err"]))
     cli.log("Overall avg like per frame (Gaussian only) = %s over %s frames." % (
-        _g(tot["like"] / tot["t"] if tot["t"] else float("nan")), ("%d" % tot["t"]) if ali else _g(tot["t"])))
+        kt.g(tot["like"] / tot["t"] if tot["t"] else float("nan")), ("%d" % tot["t"]) if ali else kt.g(tot["t"])))
     acc = state["acc"]
     if acc is None:                       # nothing accumulated: the zero accumulators of Init (twofeats: never initialised)
         off = np.asarray(am["pdf_offsets"], np.int32)
@@ -241,26 +186,27 @@ def run_acc_stats(cli, argv, prog):
         if two and new_dim == 0:
             acc = dict(acc, pdf_offsets=np.zeros(1, np.int32))
     acc["transition_accs"] = state["trans"]
-    _write_accs(cli, kio, po.get_arg(5 if two else 4), acc, po["binary"])
+    # Output ko(accs_wxfilename, binary); transition_accs.Write; gmm_accs.Write
+    cli.write_kaldi_object(po.get_arg(5 if two else 4), po["binary"], lambda f: kio.write_gmm_accs(f, acc, po["binary"]))
     cli.log("Written accs.")
     return 0 if n["done"] != 0 else 1
 
 
 # ---------------------------------------------------------------- gmm-sum-accs
 def run_sum_accs(cli, argv, prog):
-    po = _options(cli, argv, prog, lambda n: n >= 2, lambda po: po.register("binary", True, "Write output in binary mode"))
+    po = kt.parse(cli, prog, USAGE[prog], argv, lambda po: po.register("binary", True, "Write output in binary mode"), lambda n: n >= 2)
     if po is None:
         return 1
-    _, kio = _mods()
+    kio = importlib.import_module("old-kaldi-git_amd.kaldi_io")
     acc = None
     for i in range(2, po.num_args() + 1):
         acc = cli.read_kaldi_object(po.get_arg(i), lambda s, b: kio.read_gmm_accs(s, b, add_into=acc))
-    _write_accs(cli, kio, po.get_arg(1), acc, po["binary"])
+    cli.write_kaldi_object(po.get_arg(1), po["binary"], lambda f: kio.write_gmm_accs(f, acc, po["binary"]))
     count = np.float32(acc["total_frames"])                          # BaseFloat TotCount()
     with np.errstate(invalid="ignore", divide="ignore"):
         avg = np.float32(acc["total_like"]) / count
-    cli.log("Summed %d stats, total count %s, avg like/frame %s" % (po.num_args() - 1, _g(count), _g(avg)))
-    cli.log("Total count of stats is %s" % _g(np.float32(acc["occ"].sum())))
+    cli.log("Summed %d stats, total count %s, avg like/frame %s" % (po.num_args() - 1, kt.g(count), kt.g(avg)))
+    cli.log("Total count of stats is %s" % kt.g(np.float32(acc["occ"].sum())))
     cli.log("Written stats to " + po.get_arg(1))
     return 0
 

@@ -28,7 +28,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from tools.lattice_scale import scale_compact_lattice   # noqa: E402
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "gmm-rescore-lattice"
 USAGE = ("Replace the acoustic scores on a lattice using a new model.\n"
          "Usage: gmm-rescore-lattice [options] <model-in> <lattice-rspecifier> <feature-rspecifier> <lattice-wspecifier>\n"
          " e.g.: gmm-rescore-lattice 1.mdl ark:1.lats scp:trn.scp ark:2.lats\n")
@@ -40,49 +42,24 @@ def acoustic_lattice_scale(scale):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    prog = "gmm-rescore-lattice"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:     # "catch(const std::exception &e) { std::cerr << e.what(); return -1; }"
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()               # before anything initialises the GPU
-    sharding = importlib.import_module("old-kaldi-git_amd.sharding")
-    po = cli.ParseOptions(USAGE)
-    po.register("old-acoustic-scale", 0.0, "Add in the scores in the input lattices with this scale, rather than discarding them.", float)
-    po.register("batch-frames", 200000, "[MI355X] frames per library call (bounds the frame x pdf matrix)", int)
-    po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
-    po.register("world", 0, "[MI355X] number of ranks sharing the job (default: WORLD_SIZE, else 1).  Rank r is the recipe's JOB r + 1: "
-                "every JOB in the arguments becomes r + 1 (run.pl JOB=1:$nj)", int)
-    po.register("rank", -1, "[MI355X] this process's rank (default: RANK, else 0)", int)
-    w_opt = r_opt = None
-    for a in argv[1:]:
-        if a.startswith("--world="):
-            w_opt = int(a.split("=", 1)[1])
-        elif a.startswith("--rank="):
-            r_opt = int(a.split("=", 1)[1])
-    rank, world = sharding.tool_ranks(w_opt or 0, -1 if r_opt is None else r_opt)
-    raw_pos = [a for a in argv[1:] if not a.startswith("--")]
-    if world > 1:
-        argv = [argv[0]] + sharding.job_substitute(argv[1:], rank)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 4:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("old-acoustic-scale", 0.0, "Add in the scores in the input lattices with this scale, rather than discarding them.", float)
+        po.register("batch-frames", 200000, "[MI355X] frames per library call (bounds the frame x pdf matrix)", int)
+        kt.register_gpu(po)
+        kt.register_ranks(po)
+    argv, rank, world, raw_pos = kt.rank_substitute(argv)
+    po = kt.parse(cli, PROG, USAGE, argv, register, 4)
+    if po is None:
         return 1
     if world > 1 and not ("JOB" in raw_pos[1] and "JOB" in raw_pos[3]):
         raise cli.KaldiError("--world=%d: the lattice tables need JOB in their names (lat.tmp.JOB.gz, lat.JOB.gz): every rank "
                              "rescores its own job's table" % world)
     kio = importlib.import_module("old-kaldi-git_amd.kaldi_io")
-    tm, am = cli.read_kaldi_object(po.get_arg(1), lambda s, b: (kio.read_transition_model(s, b), kio.read_am_diag_gmm(s, b)))
+    tm, am = kt.read_gmm_model(cli, kio, po.get_arg(1))
     feature_reader = cli.RandomAccessTableReader(po.get_arg(3), "matrix")
     lattice_reader = cli.SequentialTableReader(po.get_arg(2), "compact_lattice_converted")
     writer = cli.TableWriter(po.get_arg(4), "compact_lattice")
@@ -92,18 +69,13 @@ def run(cli, argv, prog):
     state = {}
 
     def flush(batch):
-        if not batch:
-            return
-        import torch
         api = importlib.import_module("old-kaldi-git_amd.api")
         if "gmm" not in state:
-            api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
-            gconsts, _ = api.gmm_compute_gconsts(am["weights"], am["means_invvars"], am["inv_vars"])
-            state["gmm"] = api.AmDiagGmm(gconsts, am["means_invvars"], am["inv_vars"], am["pdf_offsets"])
-        mats = [m for _, _, m in batch if m.shape[0] > 0]
-        feats = np.ascontiguousarray(np.concatenate(mats, 0), dtype=np.float32) if mats else np.zeros((0, am["dim"]), np.float32)
+            kt.select_gpu(api, po)
+            state["gmm"] = kt.device_gmm(api, am)
+        feats = kt.stack_rows([m for _, _, m in batch if m.shape[0] > 0], am["dim"])
         rows = np.concatenate([[0], np.cumsum([m.shape[0] for _, _, m in batch])]).astype(np.int64)
-        res = api.gmm_rescore_compact_lattices(state["gmm"], torch.from_numpy(feats).cuda(), rows, [c for _, c, _ in batch], tm["tid2pdf"])
+        res = api.gmm_rescore_compact_lattices(state["gmm"], feats, rows, [c for _, c, _ in batch], tm["tid2pdf"])
         where = "RescoreCompactLatticeInternal()"
         for (key, clat, m), r in zip(batch, res):
             st = r["status"]
@@ -130,23 +102,21 @@ def run(cli, argv, prog):
                 cli.warn("Lattice %s has a transition-id outside 1..%d (the reference reads past the model here). Skipping"
                          % (key, len(tm["tid2pdf"]) - 1), where)
 
-    batch, frames = [], 0
-    for key, clat in lattice_reader:
-        if not feature_reader.has_key(key):
-            cli.warn("No feature found for utterance %s. Skipping" % key)
-            tot["err"] += 1
-            continue
-        feats = feature_reader.value(key)
-        if feats.shape[0] > 0 and feats.shape[1] != am["dim"]:
-            raise cli.KaldiError("Dim mismatch: data dim = %d vs. model dim = %d" % (feats.shape[1], am["dim"]))
-        if old_scale != np.float32(1.0):
-            clat = scale_compact_lattice(scale, clat)
-        batch.append((key, clat, feats))
-        frames += feats.shape[0]
-        if frames >= po["batch-frames"]:
-            flush(batch)
-            batch, frames = [], 0
-    flush(batch)
+    def lattices():
+        for key, clat in lattice_reader:
+            if not feature_reader.has_key(key):
+                cli.warn("No feature found for utterance %s. Skipping" % key)
+                tot["err"] += 1
+                continue
+            feats = feature_reader.value(key)
+            if feats.shape[0] > 0 and feats.shape[1] != am["dim"]:
+                raise cli.KaldiError("Dim mismatch: data dim = %d vs. model dim = %d" % (feats.shape[1], am["dim"]))
+            if old_scale != np.float32(1.0):
+                clat = scale_compact_lattice(scale, clat)
+            yield key, clat, feats
+
+    for batch in kt.batches(lattices(), lambda b: b[2].shape[0], po["batch-frames"], "after"):
+        flush(batch)
     writer.close()
     cli.log("Done %d lattices with errors on %d, #frames is %d" % (tot["done"], tot["err"], tot["frames"]))
     return 0 if tot["done"] != 0 else 1

@@ -17,7 +17,7 @@ utterance was decoded, 1 if none, 255 on an error - "return -1").  Run through n
 Differences from the binary: utterances are decoded in batches (--batch-frames, not a reference option) — one forward
 pass and one decoder launch per batch, the determinization of a batch on host threads while its decode kernel runs — the
 results per utterance are the same (tests/test_gpu_latgen_tool.py); a table of per-utterance FSTs as <fst-in> is refused.
-Pipe children are started by a helper process forked before the GPU is initialised (kaldi_cli.start_pipe_helper)."""
+Pipe children are started by a helper process forked before the GPU is initialised (kaldi_tool.parse)."""
 import importlib
 import os
 import sys
@@ -26,6 +26,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
 USAGE = {
     "nnet2": ("Generate lattices using neural net model.\n"
@@ -121,17 +122,9 @@ def write_utterance(cli, api, dec, u, utt, num_rows, po, writers, word_syms, tot
 
 
 def main(argv=None, kind="nnet2"):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
     prog = "nnet-latgen-faster" if kind == "nnet2" else "gmm-latgen-faster"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, kind, prog)
-    except cli.KaldiError as e:           # "catch(const std::exception &e) { std::cerr << e.what(); return -1; }"
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        leave_group_after_failure()
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    # KaldiError alone: a ValueError (a bad --rank) is not caught here (DESIGN.md "Command line")
+    return kt.run_tool(prog, lambda cli, argv: run(cli, argv, kind, prog), argv, (kt.cli.KaldiError,), on_error=leave_group_after_failure)
 
 
 def leave_group_after_failure():
@@ -156,49 +149,31 @@ def leave_group_after_failure():
 
 
 def run(cli, argv, kind, prog):
-    cli.start_pipe_helper()               # before anything initialises the GPU
-    po = cli.ParseOptions(USAGE[kind])
+    def register(po):
+        register_decoder_options(po)
+        po.register("acoustic-scale", 0.1, "Scaling factor for acoustic likelihoods", float)
+        po.register("word-symbol-table", "", "Symbol table for words [for debug output]")
+        po.register("allow-partial", False, "If true, produce output even if end state was not reached.")
+        # not options of the reference binary:
+        po.register("batch-frames", 200000, "[MI355X] frames per forward pass / decoder launch", int)
+        po.register("reference-order", True, "[MI355X] decode in LatticeFasterDecoder's own iteration order (HashList order, running next_cutoff): the lattices the "
+                    "reference binary itself writes, bit for bit (the default since round 6)")
+        po.register("canonical-order", False, "[MI355X] opt out of --reference-order: the order-independent acceptance rule (a cheaper kernel; same 1-best on every "
+                    "recipe-like case measured, 0-6 % different raw-lattice arcs; DESIGN.md).  KH_DECODER_ORDER=reference|canonical in the "
+                    "environment overrides both")
+        kt.register_gpu(po, "[MI355X] device ordinal (CuDevice::SelectGpuId); -1: LOCAL_RANK, else 0")
+        kt.register_ranks(po, "[MI355X] number of ranks sharing the job (default: WORLD_SIZE, else 1).  Rank r is the recipe's JOB "
+                          "r + 1: every JOB in the arguments becomes r + 1 (run.pl JOB=1:$nj); a feature table without JOB is taken "
+                          "round-robin by utterance")
+        po.register("dry-run", False, "[MI355X] read the inputs and the shard, decode nothing, write nothing into the lattices "
+                    "(multi-rank plumbing test without a GPU)")
     t_start = time.time()
-    register_decoder_options(po)
-    po.register("acoustic-scale", 0.1, "Scaling factor for acoustic likelihoods", float)
-    po.register("word-symbol-table", "", "Symbol table for words [for debug output]")
-    po.register("allow-partial", False, "If true, produce output even if end state was not reached.")
-    # not options of the reference binary:
-    po.register("batch-frames", 200000, "[MI355X] frames per forward pass / decoder launch", int)
-    po.register("reference-order", True, "[MI355X] decode in LatticeFasterDecoder's own iteration order (HashList order, running next_cutoff): the lattices the "
-                "reference binary itself writes, bit for bit (the default since round 6)")
-    po.register("canonical-order", False, "[MI355X] opt out of --reference-order: the order-independent acceptance rule (a cheaper kernel; same 1-best on every "
-                "recipe-like case measured, 0-6 % different raw-lattice arcs; DESIGN.md).  KH_DECODER_ORDER=reference|canonical in the "
-                "environment overrides both")
-    po.register("gpu", -1, "[MI355X] device ordinal (CuDevice::SelectGpuId); -1: LOCAL_RANK, else 0", int)
-    po.register("world", 0, "[MI355X] number of ranks sharing the job (default: WORLD_SIZE, else 1).  Rank r is the recipe's JOB "
-                "r + 1: every JOB in the arguments becomes r + 1 (run.pl JOB=1:$nj); a feature table without JOB is taken "
-                "round-robin by utterance", int)
-    po.register("rank", -1, "[MI355X] this process's rank (default: RANK, else 0)", int)
-    po.register("dry-run", False, "[MI355X] read the inputs and the shard, decode nothing, write nothing into the lattices "
-                "(multi-rank plumbing test without a GPU)")
-    sharding = importlib.import_module("old-kaldi-git_amd.sharding")
-    # run.pl replaces JOB in the WHOLE command line (options too: --config=$dir/JOB/decode.conf, --word-symbol-table=...):
-    # so --world / --rank are looked at first, the substitution is applied to every argument, then the options are parsed
-    pre = cli.ParseOptions("")
-    pre.register("world", 0, "", int)
-    pre.register("rank", -1, "", int)
-    w_opt = r_opt = None
-    for a in argv[1:]:
-        if a.startswith("--world="):
-            w_opt = int(a.split("=", 1)[1])
-        elif a.startswith("--rank="):
-            r_opt = int(a.split("=", 1)[1])
-    rank, world = sharding.tool_ranks(w_opt or 0, -1 if r_opt is None else r_opt)
-    raw_args = list(argv)
-    if world > 1:
-        argv = [argv[0]] + sharding.job_substitute(argv[1:], rank)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() < 4 or po.num_args() > 6:
-        po.print_usage()
+    # JOB is replaced in the options too (--config=$dir/JOB/decode.conf, --word-symbol-table=...)
+    argv, rank, world, raw_pos = kt.rank_substitute(argv)
+    po = kt.parse(cli, prog, USAGE[kind], argv, register, range(4, 7))
+    if po is None:
         return 1
-    raw_pos = [a for a in raw_args[1:] if not a.startswith("--")]
+    sharding = importlib.import_module("old-kaldi-git_amd.sharding")
     had_job = ["JOB" in a for a in raw_pos] + [False] * 6
     if world > 1:
         # an EMPTY optional output ("" for the words table) is legal and writes nothing: only real outputs need JOB
@@ -217,7 +192,7 @@ def run(cli, argv, kind, prog):
     if kind == "nnet2":
         tm, (comps, priors) = cli.read_kaldi_object(model_rx, lambda s, b: (kio.read_transition_model(s, b), kio.read_am_nnet(s, b)))
     else:
-        tm, am = cli.read_kaldi_object(model_rx, lambda s, b: (kio.read_transition_model(s, b), kio.read_am_diag_gmm(s, b)))
+        tm, am = kt.read_gmm_model(cli, kio, model_rx)
     determinize = po["determinize-lattice"]
     lat_w = cli.TableWriter(lat_wspec, "compact_lattice" if determinize else "lattice")
     if not lat_w.is_open():
@@ -253,7 +228,7 @@ def run(cli, argv, kind, prog):
     # ---- the GPU from here on
     import torch
     api = importlib.import_module("old-kaldi-git_amd.api")
-    api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
+    kt.select_gpu(api, po)
     acwt = po["acoustic-scale"]
     if kind == "nnet2":
         nnet = api.Nnet(comps, priors)
@@ -262,8 +237,7 @@ def run(cli, argv, kind, prog):
         def score(feats, off):     # DecodableAmNnet (decodable-am-nnet.h:60-69), batched
             return nnet.compute(feats, off, pad_input=True, epilogue=True, prob_scale=acwt)[0]
     else:
-        gconsts, _ = api.gmm_compute_gconsts(am["weights"], am["means_invvars"], am["inv_vars"])   # DiagGmm::Read :755
-        gmm = api.AmDiagGmm(gconsts, am["means_invvars"], am["inv_vars"], am["pdf_offsets"])
+        gmm = kt.device_gmm(api, am)
         input_dim = am["dim"]
 
         def score(feats, off):     # DecodableAmDiagGmmScaled::LogLikelihood (decodable-am-diag-gmm.h:142-145)
@@ -306,8 +280,6 @@ def run(cli, argv, kind, prog):
     fst = api.Fst(graph)
 
     def flush(batch):
-        if not batch:
-            return
         off = np.concatenate([[0], np.cumsum([len(m) for _, m in batch])]).astype(np.int32)
         feats = torch.from_numpy(np.concatenate([m for _, m in batch], 0).astype(np.float32)).cuda()
         loglikes = score(feats, off)
@@ -323,22 +295,20 @@ def run(cli, argv, kind, prog):
         for u, (utt, m) in enumerate(batch):
             write_utterance(cli, api, dec, u, utt, len(m), po, (lat_w, words_w, ali_w), word_syms, totals, prog)
 
-    batch, frames = [], 0
-    for k, (utt, m) in enumerate(reader):
-        if round_robin and k % world != rank:
-            continue
-        if m.shape[0] == 0:
-            cli.warn("Zero-length utterance: " + utt)
-            totals[3] += 1
-            continue
-        if m.shape[1] != input_dim:
-            raise cli.KaldiError("feature dimension %d of %s does not match the model's input %d" % (m.shape[1], utt, input_dim))
-        batch.append((utt, m))
-        frames += m.shape[0]
-        if frames >= po["batch-frames"]:
-            flush(batch)
-            batch, frames = [], 0
-    flush(batch)
+    def utterances():
+        for k, (utt, m) in enumerate(reader):
+            if round_robin and k % world != rank:
+                continue
+            if m.shape[0] == 0:
+                cli.warn("Zero-length utterance: " + utt)
+                totals[3] += 1
+                continue
+            if m.shape[1] != input_dim:
+                raise cli.KaldiError("feature dimension %d of %s does not match the model's input %d" % (m.shape[1], utt, input_dim))
+            yield utt, m
+
+    for batch in kt.batches(utterances(), lambda b: b[1].shape[0], po["batch-frames"], "after"):
+        flush(batch)
     ok = lat_w.close()
     words_w.close()
     ali_w.close()

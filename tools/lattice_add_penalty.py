@@ -13,7 +13,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-add-penalty"
 USAGE = ("Add word insertion penalty to the lattice.\n"
          "Note: penalties are negative log-probs, base e, and are added to the\n"
          "'language model' part of the cost.\n"
@@ -32,26 +34,12 @@ def add_word_ins_pen(penalty, clat):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-add-penalty"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("word-ins-penalty", 0.0, "Word insertion penalty", float)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 2:
-        po.print_usage()
+def run(cli, argv):
+    po = kt.parse(cli, PROG, USAGE, argv, lambda po: po.register("word-ins-penalty", 0.0, "Word insertion penalty", float), 2)
+    if po is None:
         return 1
     reader = cli.SequentialTableReader(po.get_arg(1), "compact_lattice")
     writer = cli.TableWriter(po.get_arg(2), "compact_lattice")

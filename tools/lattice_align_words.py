@@ -19,7 +19,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-align-words"
 USAGE = ("Convert lattices so that the arcs in the CompactLattice format correspond with\n"
          "words (i.e. aligned with word boundaries).  Note: it will generally be more\n"
          "efficient if you apply 'lattice-push' before this program.\n"
@@ -33,29 +35,7 @@ USAGE = ("Convert lattices so that the arcs in the CompactLattice format corresp
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-align-words"
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
-
-
-def batches(reader, batch_arcs):
-    batch, arcs = [], 0
-    for key, clat in reader:
-        batch.append((key, clat))
-        arcs += len(clat["arc_src"])
-        if arcs >= batch_arcs:
-            yield batch
-            batch, arcs = [], 0
-    if batch:
-        yield batch
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH)
 
 
 def not_deterministic(clat):
@@ -68,26 +48,23 @@ def not_deterministic(clat):
     return len(np.unique(key)) != len(key)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("output-error-lats", True, "Output lattices that aligned with errors (e.g. due to force-out", bool)
-    po.register("test", False, "Test the algorithm while running it.", bool)
-    po.register("max-expand", 0.0, "If >0, the maximum amount by which this program will expand lattices before refusing to "
-                "continue.  E.g. 10.This can be used to prevent this program consuming excessive memory if there is a mismatch "
-                "on the command-line or a 'problem' lattice.", float)
-    po.register("silence-label", 0, "Numeric id of word symbol that is to be used for silence arcs in the word-aligned "
-                "lattice (zero is OK)", int)
-    po.register("partial-word-label", 0, "Numeric id of word symbol that is to be used for arcs in the word-aligned lattice "
-                "corresponding to partial words at the end of \"forced-out\" utterances (zero is OK)", int)
-    po.register("reorder", True, "True if the lattices were generated from graphs that had the --reorder option true, "
-                "relating to reordering self-loops (typically true)", bool)
-    po.register("batch-arcs", 200000, "[MI355X] lattice arcs per call", int)
-    po.register("gpu", -1, "[MI355X] device ordinal; -1: LOCAL_RANK, else 0", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 4:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("output-error-lats", True, "Output lattices that aligned with errors (e.g. due to force-out", bool)
+        po.register("test", False, "Test the algorithm while running it.", bool)
+        po.register("max-expand", 0.0, "If >0, the maximum amount by which this program will expand lattices before refusing to "
+                    "continue.  E.g. 10.This can be used to prevent this program consuming excessive memory if there is a mismatch "
+                    "on the command-line or a 'problem' lattice.", float)
+        po.register("silence-label", 0, "Numeric id of word symbol that is to be used for silence arcs in the word-aligned "
+                    "lattice (zero is OK)", int)
+        po.register("partial-word-label", 0, "Numeric id of word symbol that is to be used for arcs in the word-aligned lattice "
+                    "corresponding to partial words at the end of \"forced-out\" utterances (zero is OK)", int)
+        po.register("reorder", True, "True if the lattices were generated from graphs that had the --reorder option true, "
+                    "relating to reordering self-loops (typically true)", bool)
+        po.register("batch-arcs", 200000, "[MI355X] lattice arcs per call", int)
+        kt.register_gpu(po)
+    po = kt.parse(cli, PROG, USAGE, argv, register, 4)
+    if po is None:
         return 1
     if po["test"]:
         raise cli.KaldiError("--test=true is not provided: TestWordAlignedLattice's RandEquivalent draws from the C library's "
@@ -102,10 +79,10 @@ def run(cli, argv, prog):
         wbinfo = kio.parse_word_boundary_info(f.read(), po["reorder"], po["silence-label"], po["partial-word-label"])
     finally:
         cli._close(f, kind)
-    api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
+    kt.select_gpu(api, po)
     max_expand = np.float32(po["max-expand"])
     n_done, n_err = 0, 0
-    for batch in batches(reader, po["batch-arcs"]):
+    for batch in kt.batches(reader, lambda b: len(b[1]["arc_src"]), po["batch-arcs"], "after"):
         if max_expand > 0:                                                                          # :90: int32 = float
             ms = [int(np.float32(1000) + max_expand * np.float32(int(c["n_states"]))) for _, c in batch]
         else:

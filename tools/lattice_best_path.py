@@ -23,7 +23,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-best-path"
 USAGE = ("Generate 1-best path through lattices; output as transcriptions and alignments\n"
          "Note: if you want output as FSTs, use lattice-1best; if you want output\n"
          "with acoustic and LM scores, use lattice-1best | nbest-to-linear\n"
@@ -31,61 +33,23 @@ USAGE = ("Generate 1-best path through lattices; output as transcriptions and al
          " e.g.: lattice-best-path --acoustic-scale=0.1 ark:1.lats ark:1.tra ark:1.ali\n")
 
 
-def parse_sweep_list(text, what):
-    """"9:20" (integers, both ends included) or "9,10.5,12" -> the tokens as typed."""
-    text = text.strip()
-    if ":" in text:
-        lo, _, hi = text.partition(":")
-        try:
-            lo, hi = int(lo), int(hi)
-        except ValueError:
-            raise ValueError("Invalid %s range %r (expected first:last, integers)" % (what, text))
-        if hi < lo:
-            raise ValueError("Invalid %s range %r (empty)" % (what, text))
-        return [str(v) for v in range(lo, hi + 1)]
-    toks = [t.strip() for t in text.split(",")]
-    for t in toks:
-        try:
-            float(t)
-        except ValueError:
-            raise ValueError("Invalid %s list %r" % (what, text))
-    return toks
-
-
-def substitute(wspecifier, lmwt, wip):
-    return wspecifier.replace("LMWT", lmwt).replace("WIP", wip)
-
-
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-best-path"
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
-    po.register("lm-scale", 1.0, "Scaling factor for LM probabilities. Note: the ratio acoustic-scale/lm-scale is all that matters.", float)
-    po.register("word-symbol-table", "", "Symbol table for words [for debug output]", str)
-    po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
-                "--inv-acoustic-scale before the search, LMWT in the wspecifiers stands for it", str)
-    po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
-                "before the search, WIP in the wspecifiers stands for it", str)
-    po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per best-path call", int)
-    po.register("gpu", 0, "[MI355X] device ordinal", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() < 1 or po.num_args() > 3:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
+        po.register("lm-scale", 1.0, "Scaling factor for LM probabilities. Note: the ratio acoustic-scale/lm-scale is all that matters.", float)
+        po.register("word-symbol-table", "", "Symbol table for words [for debug output]", str)
+        po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
+                    "--inv-acoustic-scale before the search, LMWT in the wspecifiers stands for it", str)
+        po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
+                    "before the search, WIP in the wspecifiers stands for it", str)
+        po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per best-path call", int)
+        po.register("gpu", 0, "[MI355X] device ordinal", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, range(1, 4))
+    if po is None:
         return 1
     api = importlib.import_module("old-kaldi-git_amd.api")
     sweep = po["inv-acoustic-scales"] != "" or po["word-ins-penalties"] != ""
@@ -93,20 +57,12 @@ def run(cli, argv, prog):
         if np.float32(po["acoustic-scale"]) != 1.0 or np.float32(po["lm-scale"]) != 1.0:
             raise cli.KaldiError("the sweep stands for lattice-scale | lattice-add-penalty | lattice-best-path with the last "
                                  "one's scales at 1.0: do not combine it with --acoustic-scale / --lm-scale")
-        lmwts = parse_sweep_list(po["inv-acoustic-scales"], "--inv-acoustic-scales") if po["inv-acoustic-scales"] else ["1"]
-        wips = parse_sweep_list(po["word-ins-penalties"], "--word-ins-penalties") if po["word-ins-penalties"] else ["0.0"]
-        names = [(l, w) for w in wips for l in lmwts]
-        points = [api.score_point(inv_acoustic_scale=float(l), word_ins_penalty=float(w)) for l, w in names]
-        specs = [(substitute(po.get_opt_arg(2), l, w), substitute(po.get_opt_arg(3), l, w)) for l, w in names]
-        for k in (0, 1):
-            used = [s[k] for s in specs if s[k] != ""]
-            if len(set(used)) != len(used):
-                raise cli.KaldiError("the sweep's wspecifiers must differ per point (use LMWT and WIP in them): %s" % used[0])
+        points, specs, tag = kt.score_sweep(cli, api, po, (2, 3))
     else:
         # fst::LatticeScale(lm_scale, acoustic_scale) :85 (the options are floats, the matrix holds doubles)
-        names = [None]
         points = [api.score_point(lm_scale=po["lm-scale"], acoustic_scale=po["acoustic-scale"])]
         specs = [(po.get_opt_arg(2), po.get_opt_arg(3))]
+        tag = lambda p: ""
     K = len(points)
     reader = cli.SequentialTableReader(po.get_arg(1), "compact_lattice")
     word_w = [cli.TableWriter(s[0], "int32_vector") for s in specs]
@@ -116,15 +72,12 @@ def run(cli, argv, prog):
     f32 = np.float32
     n_done, n_fail, n_frame = [0] * K, [0] * K, [0] * K
     tot_g, tot_a = [f32(0.0)] * K, [f32(0.0)] * K        # LatticeWeight::One() :79
-    tag = lambda p: "" if names[p] is None else "[LMWT=%s WIP=%s] " % names[p]
 
     def fail(key, p):
         cli.warn("%sBest-path failed for key %s" % (tag(p), key))
         n_fail[p] += 1
 
     def flush(batch):
-        if not batch:
-            return
         res = api.compact_lattice_best_paths([c for _, c in batch], points)
         for (key, _), row in zip(batch, res):
             for p, r in enumerate(row):
@@ -152,18 +105,16 @@ def run(cli, argv, prog):
                 tot_g[p] = tot_g[p] + g
                 tot_a[p] = tot_a[p] + a
 
-    batch, arcs = [], 0
-    for key, clat in reader:
-        if int(clat["n_states"]) == 0 or int(clat.get("start", 0)) < 0:      # :1055: no start state, empty best path
-            for p in range(K):
-                fail(key, p)
-            continue
-        batch.append((key, clat))
-        arcs += len(clat["arc_src"])
-        if arcs >= po["batch-arcs"]:
-            flush(batch)
-            batch, arcs = [], 0
-    flush(batch)
+    def lattices():
+        for key, clat in reader:
+            if int(clat["n_states"]) == 0 or int(clat.get("start", 0)) < 0:      # :1055: no start state, empty best path
+                for p in range(K):
+                    fail(key, p)
+                continue
+            yield key, clat
+
+    for batch in kt.batches(lattices(), lambda b: len(b[1]["arc_src"]), po["batch-arcs"], "after"):
+        flush(batch)
     for w in word_w + ali_w:
         w.close()
     with np.errstate(divide="ignore", invalid="ignore"):

@@ -24,9 +24,10 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from tools.lattice_best_path import parse_sweep_list          # noqa: E402
-from tools.lattice_oracle import beam_specs, cxx_ratio        # noqa: E402
+from tools.lattice_oracle import cxx_ratio        # noqa: E402
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-depth"
 USAGE = ("Compute the lattice depths in terms of the average number of arcs that\n"
          "cross a frame.  See also lattice-depth-per-frame\n"
          "Usage: lattice-depth <lattice-rspecifier> [<depth-wspecifier>]\n"
@@ -34,85 +35,52 @@ USAGE = ("Compute the lattice depths in terms of the average number of arcs that
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-depth"
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    except AssertionError as e:       # KALDI_ASSERT aborts
-        sys.stderr.write("%s\n" % e)
-        return 134
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH, assert_status=134)          # KALDI_ASSERT aborts
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "[MI355X] with --beams: as lattice-prune --acoustic-scale in front of this program", float)
-    po.register("beams", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-prune --beam in front of this "
-                "program, BEAM in the wspecifier stands for it", str)
-    po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per device call", int)
-    po.register("gpu", 0, "[MI355X] device ordinal", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() < 1 or po.num_args() > 2:                                 # :48
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "[MI355X] with --beams: as lattice-prune --acoustic-scale in front of this program", float)
+        po.register("beams", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-prune --beam in front of this "
+                    "program, BEAM in the wspecifier stands for it", str)
+        po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per device call", int)
+        po.register("gpu", 0, "[MI355X] device ordinal", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, range(1, 3))               # :48
+    if po is None:
         return 1
     sweep = po["beams"] != ""
-    beams = parse_sweep_list(po["beams"], "--beams") if sweep else [None]
+    beams, (specs,), tag = kt.beam_sweep(cli, po, (po.get_opt_arg(2),))
     K = len(beams)
-    spec = po.get_opt_arg(2)
-    if sweep:
-        for b in beams:
-            if not np.float32(float(b)) > 0.0:                                 # KALDI_ASSERT(beam > 0.0), PruneLattice :192
-                raise AssertionError("KALDI_ASSERT: at PruneLattice:lattice-functions.cc:192, failed: beam > 0.0")
-        if np.float32(po["acoustic-scale"]) == 0.0:
-            raise cli.KaldiError("Do not use a zero acoustic scale (cannot be inverted)")
-        if spec != "" and len(set(beam_specs(spec, beams))) != K:
-            raise cli.KaldiError("the sweep's wspecifiers must differ per point (use BEAM in them): %s" % spec)
-    elif np.float32(po["acoustic-scale"]) != 1.0:
-        raise cli.KaldiError("--acoustic-scale belongs to the sweep: give --beams with it")
     reader = cli.SequentialTableReader(po.get_arg(1), "compact_lattice")
-    writers = [cli.TableWriter(s, "base_float") for s in (beam_specs(spec, beams) if sweep else [spec])]
+    writers = [cli.TableWriter(s, "base_float") for s in specs]
     api = importlib.import_module("old-kaldi-git_amd.api")
     if sweep:
         api.select_gpu(po["gpu"])
     point = api.score_point(acoustic_scale=po["acoustic-scale"])
     num_done = 0                                                               # :59
     sum_depth, total_t = [0.0] * K, [0.0] * K                                  # :60
-    tag = lambda p: "" if beams[p] is None else "[BEAM=%s] " % beams[p]
 
     def account(p, key, depth, t):
         writers[p].write(key, np.float32(depth))                               # :70-71
         sum_depth[p] += float(np.float32(depth) * np.float32(t))               # :73 (a float product)
         total_t[p] += t                                                        # :74
 
-    def flush(batch):
-        if not batch:
-            return
+    def lattices():
+        """The plain command line accounts for a lattice as it is read; the sweep's lattices go on to the device call."""
+        nonlocal num_done
+        for key, clat in reader:
+            num_done += 1                                                      # :75
+            if not sweep:
+                depth, t = api.compact_lattice_depth(clat)                     # :65-68
+                account(0, key, depth, t)
+                continue
+            yield key, clat
+
+    for batch in kt.batches(lattices(), lambda b: len(b[1]["arc_src"]), po["batch-arcs"], "after"):
         res = api.compact_lattice_oracle([c for _, c in batch], [[] for _ in batch], (), points=[point], beams=[float(b) for b in beams])
         for (key, _), row in zip(batch, res):
             for p, r in enumerate(row):
                 account(p, key, r["depth"], r["num_frames"])
-
-    batch, arcs = [], 0
-    for key, clat in reader:
-        num_done += 1                                                          # :75
-        if not sweep:
-            depth, t = api.compact_lattice_depth(clat)                         # :65-68
-            account(0, key, depth, t)
-            continue
-        batch.append((key, clat))
-        arcs += len(clat["arc_src"])
-        if arcs >= po["batch-arcs"]:
-            flush(batch)
-            batch, arcs = [], 0
-    flush(batch)
     for w in writers:
         w.close()
     cli.log("Done %d lattices." % num_done)                                    # :77

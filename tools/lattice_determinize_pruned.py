@@ -22,7 +22,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from tools.lattice_scale import scale_weights   # noqa: E402
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-determinize-pruned"
 USAGE = ("Determinize lattices, keeping only the best path (sequence of acoustic states)\n"
          "for each input-symbol sequence.  This version does pruning as part of the\n"
          "determinization algorithm, which is more efficient and prevents blowup.\n"
@@ -63,34 +65,21 @@ def scaled_input(L, scale, warned, warn):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    prog = "lattice-determinize-pruned"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
-    po.register("beam", 10.0, "Pruning beam [applied after acoustic scaling].", float)
-    po.register("minimize", False, "If true, push and minimize after determinization")
-    po.register("delta", 2.0 ** -10, "Tolerance used in determinization", float)
-    po.register("max-mem", 50000000, "Maximum approximate memory usage in determinization (real usage might be many times this)", int)
-    po.register("max-loop", 0, "Option used to detect a particular type of determinization failure, typically due to invalid input "
-                "(e.g., negative-cost loops) [MI355X: only 0 is supported]", int)
-    po.register("num-threads", 0, "[MI355X] host threads (0: as many as the process may use)", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 2:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
+        po.register("beam", 10.0, "Pruning beam [applied after acoustic scaling].", float)
+        po.register("minimize", False, "If true, push and minimize after determinization")
+        po.register("delta", 2.0 ** -10, "Tolerance used in determinization", float)
+        po.register("max-mem", 50000000, "Maximum approximate memory usage in determinization (real usage might be many times this)", int)
+        po.register("max-loop", 0, "Option used to detect a particular type of determinization failure, typically due to invalid input "
+                    "(e.g., negative-cost loops) [MI355X: only 0 is supported]", int)
+        po.register("num-threads", 0, "[MI355X] host threads (0: as many as the process may use)", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, 2)
+    if po is None:
         return 1
     if po["max-loop"] != 0:
         raise cli.KaldiError("--max-loop=%d: the library's determinizer has no loop detection; only --max-loop=0 is supported" % po["max-loop"])
@@ -106,8 +95,6 @@ def run(cli, argv, prog):
     warned = [False]
 
     def flush(batch):
-        if not batch:
-            return
         dets = api.determinize_lattices([scaled_input(L, scale, warned, cli.warn) for _, L in batch], float(np.float32(po["beam"])),
                                         float(np.float32(po["delta"])), int(po["max-mem"]), po["num-threads"],
                                         phone_determinize=False, word_determinize=True, minimize=bool(po["minimize"]))
@@ -120,13 +107,8 @@ def run(cli, argv, prog):
             writer.write(key, det)
             n["done"] += 1
 
-    batch = []
-    for key, L in reader:
-        batch.append((key, L))
-        if len(batch) >= BATCH:
-            flush(batch)
-            batch = []
-    flush(batch)
+    for batch in kt.batches(reader, lambda b: 1, BATCH, "after"):
+        flush(batch)
     writer.close()
     cli.log("Done %d lattices, determinization finished earlier than specified by the beam on %d of these." % (n["done"], n["warn"]))
     return 0 if n["done"] != 0 else 1

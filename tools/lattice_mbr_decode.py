@@ -27,8 +27,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from tools.lattice_best_path import parse_sweep_list, substitute  # noqa: E402
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-mbr-decode"
 USAGE = ("Do Minimum Bayes Risk decoding (decoding that aims to minimize the \n"
          "expected word error rate).  Possible outputs include the 1-best path\n"
          "(i.e. the word-sequence, as a sequence of ints per utterance), the\n"
@@ -47,79 +48,37 @@ USAGE = ("Do Minimum Bayes Risk decoding (decoding that aims to minimize the \n"
          " e.g.: lattice-mbr-decode --acoustic-scale=0.1 ark:1.lats ark:1.tra ark:/dev/null ark:1.sau\n")
 
 
-def sweep_points(cli, api, po, n_specs, first_spec):
-    """The score points and the output names of a run: (names [None or (LMWT, WIP) as typed], points, specs [per point the
-    positional arguments first_spec .. first_spec + n_specs - 1 with LMWT / WIP replaced])."""
-    if po["inv-acoustic-scales"] == "" and po["word-ins-penalties"] == "":
-        return None
-    lmwts = parse_sweep_list(po["inv-acoustic-scales"], "--inv-acoustic-scales") if po["inv-acoustic-scales"] else ["1"]
-    wips = parse_sweep_list(po["word-ins-penalties"], "--word-ins-penalties") if po["word-ins-penalties"] else ["0.0"]
-    names = [(l, w) for w in wips for l in lmwts]
-    points = [api.score_point(inv_acoustic_scale=float(l), word_ins_penalty=float(w)) for l, w in names]
-    specs = [tuple(substitute(po.get_opt_arg(first_spec + k), l, w) for k in range(n_specs)) for l, w in names]
-    for k in range(n_specs):
-        used = [s[k] for s in specs if s[k] != ""]
-        if len(set(used)) != len(used):
-            raise cli.KaldiError("the sweep's outputs must differ per point (use LMWT and WIP in them): %s" % used[0])
-    return names, points, specs
-
-
-def batches(reader, batch_arcs):
-    batch, arcs = [], 0
-    for key, clat in reader:
-        batch.append((key, clat))
-        arcs += len(clat["arc_src"])
-        if arcs >= batch_arcs:
-            yield batch
-            batch, arcs = [], 0
-    if batch:
-        yield batch
-
-
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-mbr-decode"
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
-    po.register("lm-scale", 1.0, "Scaling factor for language model probabilities", float)
-    po.register("word-symbol-table", "", "Symbol table for words [for debug output]", str)
-    po.register("one-best-times", False, "If true, output times corresponding to one-best, not whole sausage.", bool)
-    po.register("one-best-rspecifier", "", "[MI355X] initial hypotheses (int32 vectors) in place of the lattices' best paths", str)
-    po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
-                "--inv-acoustic-scale before the decoding, LMWT in the wspecifiers stands for it", str)
-    po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
-                "before the decoding, WIP in the wspecifiers stands for it", str)
-    po.register("batch-arcs", 200000, "[MI355X] lattice arcs per call", int)
-    po.register("gpu", 0, "[MI355X] device ordinal", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() < 2 or po.num_args() > 5:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
+        po.register("lm-scale", 1.0, "Scaling factor for language model probabilities", float)
+        po.register("word-symbol-table", "", "Symbol table for words [for debug output]", str)
+        po.register("one-best-times", False, "If true, output times corresponding to one-best, not whole sausage.", bool)
+        po.register("one-best-rspecifier", "", "[MI355X] initial hypotheses (int32 vectors) in place of the lattices' best paths", str)
+        po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
+                    "--inv-acoustic-scale before the decoding, LMWT in the wspecifiers stands for it", str)
+        po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
+                    "before the decoding, WIP in the wspecifiers stands for it", str)
+        po.register("batch-arcs", 200000, "[MI355X] lattice arcs per call", int)
+        po.register("gpu", 0, "[MI355X] device ordinal", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, range(2, 6))
+    if po is None:
         return 1
     api = importlib.import_module("old-kaldi-git_amd.api")
-    sw = sweep_points(cli, api, po, 4, 2)
+    sw = kt.score_sweep(cli, api, po, (2, 3, 4, 5), "outputs")
     if sw is not None:
         if np.float32(po["acoustic-scale"]) != 1.0 or np.float32(po["lm-scale"]) != 1.0:
             raise cli.KaldiError("the sweep stands for lattice-scale | lattice-add-penalty | lattice-mbr-decode with the last "
                                  "one's scales at 1.0: do not combine it with --acoustic-scale / --lm-scale")
-        names, points, specs = sw
+        points, specs, tag = sw
     else:
-        names = [None]
         points = [api.score_point(lm_scale=po["lm-scale"], acoustic_scale=po["acoustic-scale"])]   # :101
         specs = [tuple(po.get_opt_arg(k) for k in (2, 3, 4, 5))]
+        tag = lambda p: ""
     K = len(points)
     reader = cli.SequentialTableReader(po.get_arg(1), "compact_lattice")
     one_best = cli.RandomAccessTableReader(po["one-best-rspecifier"], "int32_vector") if po["one-best-rspecifier"] != "" else None
@@ -132,8 +91,7 @@ def run(cli, argv, prog):
     api.select_gpu(po["gpu"])
     f32 = np.float32
     n_done, n_words, tot = [0] * K, [0] * K, [f32(0.0)] * K
-    tag = lambda p: "" if names[p] is None else "[LMWT=%s WIP=%s] " % names[p]
-    for batch in batches(reader, po["batch-arcs"]):
+    for batch in kt.batches(reader, lambda b: len(b[1]["arc_src"]), po["batch-arcs"], "after"):
         keep, given = [], []
         for key, clat in batch:
             if int(clat["n_states"]) == 0 or int(clat.get("start", 0)) < 0:

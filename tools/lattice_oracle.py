@@ -27,8 +27,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from tools.lattice_best_path import parse_sweep_list          # noqa: E402
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-oracle"
 USAGE = ("Finds the path having the smallest edit-distance between two lattices.\n"
          "For efficiency put the smallest lattices first (for example reference strings).\n"
          "Usage: lattice-oracle [options] <test-lattice-rspecifier> <reference-rspecifier> "
@@ -58,10 +59,6 @@ def lattice_as_word_graph(lat):
                 final_g=np.where(none, inf, fg), final_a=np.where(none, inf, fa))
 
 
-def beam_specs(spec, beams):
-    return [spec.replace("BEAM", b) for b in beams]
-
-
 def read_symbol_list(cli, rxfilename, word_syms):
     """ReadSymbolList :33-56."""
     by_name = {v: k for k, v in word_syms.items()}
@@ -82,60 +79,30 @@ def read_symbol_list(cli, rxfilename, word_syms):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-oracle"
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    except AssertionError as e:       # KALDI_ASSERT aborts
-        sys.stderr.write("%s\n" % e)
-        return 134
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH, assert_status=134)          # KALDI_ASSERT aborts
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("word-symbol-table", "", "Symbol table for words [for debug output]", str)
-    po.register("wildcard-symbols-list", "", "Filename (generally, rxfilename) for file containing text-form list of symbols that "
-                "don't count as errors; this option requires --word-symbol-table.  Deprecated; use --wildcard-symbols option.", str)
-    po.register("wildcard-symbols", "", "Colon-separated list of integer ids of symbols that don't count as errors.  Preferred "
-                "alternative to deprecated option --wildcard-symbols-list.", str)
-    po.register("write-lattices", "", "If supplied, write 1-best path as lattices to this wspecifier [not provided here]", str)
-    po.register("acoustic-scale", 1.0, "[MI355X] with --beams: as lattice-prune --acoustic-scale in front of this program", float)
-    po.register("beams", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-prune --beam in front of this "
-                "program, BEAM in the wspecifiers stands for it", str)
-    po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per device call", int)
-    po.register("gpu", 0, "[MI355X] device ordinal", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 3 and po.num_args() != 4:                              # :265
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("word-symbol-table", "", "Symbol table for words [for debug output]", str)
+        po.register("wildcard-symbols-list", "", "Filename (generally, rxfilename) for file containing text-form list of symbols that "
+                    "don't count as errors; this option requires --word-symbol-table.  Deprecated; use --wildcard-symbols option.", str)
+        po.register("wildcard-symbols", "", "Colon-separated list of integer ids of symbols that don't count as errors.  Preferred "
+                    "alternative to deprecated option --wildcard-symbols-list.", str)
+        po.register("write-lattices", "", "If supplied, write 1-best path as lattices to this wspecifier [not provided here]", str)
+        po.register("acoustic-scale", 1.0, "[MI355X] with --beams: as lattice-prune --acoustic-scale in front of this program", float)
+        po.register("beams", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-prune --beam in front of this "
+                    "program, BEAM in the wspecifiers stands for it", str)
+        po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per device call", int)
+        po.register("gpu", 0, "[MI355X] device ordinal", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, range(3, 5))               # :265
+    if po is None:
         return 1
     if po["write-lattices"] != "":
         raise cli.KaldiError("--write-lattices is not provided by this implementation")
     sweep = po["beams"] != ""
-    beams = parse_sweep_list(po["beams"], "--beams") if sweep else [None]
+    beams, (tra_specs, edit_specs), tag = kt.beam_sweep(cli, po, (po.get_arg(3), po.get_opt_arg(4)))
     K = len(beams)
-    tra_spec, edit_spec = po.get_arg(3), po.get_opt_arg(4)
-    if sweep:
-        for b in beams:
-            if not np.float32(float(b)) > 0.0:                                 # KALDI_ASSERT(beam > 0.0), PruneLattice :192
-                raise AssertionError("KALDI_ASSERT: at PruneLattice:lattice-functions.cc:192, failed: beam > 0.0")
-        if np.float32(po["acoustic-scale"]) == 0.0:
-            raise cli.KaldiError("Do not use a zero acoustic scale (cannot be inverted)")
-        for spec in (tra_spec, edit_spec):
-            if spec != "" and len(set(beam_specs(spec, beams))) != K:
-                raise cli.KaldiError("the sweep's wspecifiers must differ per point (use BEAM in them): %s" % spec)
-    elif np.float32(po["acoustic-scale"]) != 1.0:
-        raise cli.KaldiError("--acoustic-scale belongs to the sweep: give --beams with it")
-    tra_specs = beam_specs(tra_spec, beams) if sweep else [tra_spec]
-    edit_specs = beam_specs(edit_spec, beams) if sweep else [edit_spec]
 
     word_syms = None
     if po["word-symbol-table"] != "":                                          # :285-288
@@ -167,11 +134,8 @@ def run(cli, argv, prog):
     point = api.score_point(acoustic_scale=po["acoustic-scale"])
     n_done, n_fail = [0] * K, [0] * K
     tot = [dict(correct=0, sub=0, ins=0, words=0, **{"del": 0}) for _ in range(K)]
-    tag = lambda p: "" if beams[p] is None else "[BEAM=%s] " % beams[p]
 
     def flush(batch):
-        if not batch:
-            return
         clats, rws = [c for _, c, _ in batch], [r for _, _, r in batch]
         if sweep:
             res = api.compact_lattice_oracle(clats, rws, wildcards, points=[point], beams=[float(b) for b in beams])
@@ -204,21 +168,19 @@ def run(cli, argv, prog):
                             sys.stderr.write("%s%s (%s) %s\n" % (tag(p), key, what, "".join(n + " " for n in names)))
                 n_done[p] += 1                                                 # :420
 
-    batch, arcs = [], 0
-    for key, obj in reader:
-        sys.stderr.write("Lattice %s read.\n" % key)                           # :316
-        clat = obj if sweep else (obj[1] if obj[0] else lattice_as_word_graph(obj[1]))
-        if not refs.has_key(key):                                              # :325-329
-            cli.warn("No reference present for utterance " + key)
-            for p in range(K):
-                n_fail[p] += 1
-            continue
-        batch.append((key, clat, np.asarray(refs.value(key), np.int32)))
-        arcs += len(clat["arc_src"])
-        if arcs >= po["batch-arcs"]:
-            flush(batch)
-            batch, arcs = [], 0
-    flush(batch)
+    def lattices():
+        for key, obj in reader:
+            sys.stderr.write("Lattice %s read.\n" % key)                       # :316
+            clat = obj if sweep else (obj[1] if obj[0] else lattice_as_word_graph(obj[1]))
+            if not refs.has_key(key):                                          # :325-329
+                cli.warn("No reference present for utterance " + key)
+                for p in range(K):
+                    n_fail[p] += 1
+                continue
+            yield key, clat, np.asarray(refs.value(key), np.int32)
+
+    for batch in kt.batches(lattices(), lambda b: len(b[1]["arc_src"]), po["batch-arcs"], "after"):
+        flush(batch)
     for w in tra_w + edit_w:
         w.close()
     for p in range(K):

@@ -26,9 +26,10 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 from tools.lattice_add_penalty import add_word_ins_pen                   # noqa: E402
-from tools.lattice_best_path import parse_sweep_list, substitute          # noqa: E402
 from tools.lattice_scale import scale_compact_lattice                     # noqa: E402
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-prune"
 USAGE = ("Apply beam pruning to lattices\n"
          "Usage: lattice-prune [options] lattice-rspecifier lattice-wspecifier\n"
          " e.g.: lattice-prune --acoustic-scale=0.1 --beam=4.0 ark:1.lats ark:pruned.lats\n")
@@ -67,81 +68,54 @@ def pruned_subset(clat, r):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-prune"
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    except AssertionError as e:       # KALDI_ASSERT aborts
-        sys.stderr.write("%s\n" % e)
-        return 134
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH, assert_status=134)          # KALDI_ASSERT aborts
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
-    po.register("inv-acoustic-scale", 1.0, "An alternative way of setting the acoustic scale: you can set its inverse.", float)
-    po.register("beam", 10.0, "Pruning beam [applied after acoustic scaling]", float)
-    po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
-                "--inv-acoustic-scale before the pruning, LMWT in the wspecifier stands for it", str)
-    po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
-                "before the pruning, WIP in the wspecifier stands for it", str)
-    po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per pruning call", int)
-    po.register("gpu", 0, "[MI355X] device ordinal", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 2:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
+        po.register("inv-acoustic-scale", 1.0, "An alternative way of setting the acoustic scale: you can set its inverse.", float)
+        po.register("beam", 10.0, "Pruning beam [applied after acoustic scaling]", float)
+        po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
+                    "--inv-acoustic-scale before the pruning, LMWT in the wspecifier stands for it", str)
+        po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
+                    "before the pruning, WIP in the wspecifier stands for it", str)
+        po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per pruning call", int)
+        po.register("gpu", 0, "[MI355X] device ordinal", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, 2)
+    if po is None:
         return 1
     f32 = np.float32
     beam = f32(po["beam"])
+    api = importlib.import_module("old-kaldi-git_amd.api")
     sweep = po["inv-acoustic-scales"] != "" or po["word-ins-penalties"] != ""
     identity = acoustic_lattice_scale(1.0)
     if sweep:
         if f32(po["acoustic-scale"]) != 1.0 or f32(po["inv-acoustic-scale"]) != 1.0:
             raise cli.KaldiError("the sweep stands for lattice-scale | lattice-add-penalty | lattice-prune with the last one's "
                                  "scale at 1.0: do not combine it with --acoustic-scale / --inv-acoustic-scale")
-        lmwts = parse_sweep_list(po["inv-acoustic-scales"], "--inv-acoustic-scales") if po["inv-acoustic-scales"] else ["1"]
-        wips = parse_sweep_list(po["word-ins-penalties"], "--word-ins-penalties") if po["word-ins-penalties"] else ["0.0"]
-        names = [(l, w) for w in wips for l in lmwts]
-        specs = [substitute(po.get_arg(2), l, w) for l, w in names]
-        if len(set(specs)) != len(specs):
-            raise cli.KaldiError("the sweep's wspecifiers must differ per point (use LMWT and WIP in them): %s" % specs[0])
+        points, specs, tag = kt.score_sweep(cli, api, po, (2,))
+        specs = [s[0] for s in specs]
         there, back = identity, identity
     else:
         ac = plain_scale(po["acoustic-scale"], po["inv-acoustic-scale"])
         if ac == 0.0:                                                         # :75
             raise cli.KaldiError("Do not use a zero acoustic scale (cannot be inverted)")
-        names, specs = [None], [po.get_arg(2)]
         there = acoustic_lattice_scale(ac)                                    # :82
         with np.errstate(all="ignore"):
             back = acoustic_lattice_scale(np.float64(1.0) / np.float64(ac))   # :98: the double quotient
+        points, specs, tag = [(there.reshape(4), f32(0.0))], [po.get_arg(2)], lambda p: ""
     if not beam > 0.0:                                                        # KALDI_ASSERT(beam > 0.0), PruneLattice :192
         raise AssertionError("KALDI_ASSERT: at PruneLattice:lattice-functions.cc:192, failed: beam > 0.0")
-    api = importlib.import_module("old-kaldi-git_amd.api")
-    if sweep:
-        points = [api.score_point(inv_acoustic_scale=float(l), word_ins_penalty=float(w)) for l, w in names]
-    else:
-        points = [(there.reshape(4), f32(0.0))]
     K = len(points)
     reader = cli.SequentialTableReader(po.get_arg(1), "compact_lattice")
     writers = [cli.TableWriter(s, "compact_lattice") for s in specs]
     api.select_gpu(po["gpu"])
     n_done, n_err = 0, [0] * K
     n_arcs_in, n_states_in, n_arcs_out, n_states_out = 0, 0, [0] * K, [0] * K
-    tag = lambda p: "" if names[p] is None else "[LMWT=%s WIP=%s] " % names[p]
 
     def flush(batch):
         nonlocal n_done, n_arcs_in, n_states_in
-        if not batch:
-            return
         res = api.compact_lattice_prune([c for _, c in batch], points, beam)
         for (key, clat), row in zip(batch, res):
             narcs, nstates = len(clat["arc_src"]), int(clat["n_states"])      # :83
@@ -165,14 +139,8 @@ def run(cli, argv, prog):
                 writers[p].write(key, scale_compact_lattice(back, pruned))    # :98-99: every key is written
             n_done += 1                                                       # :100
 
-    batch, arcs = [], 0
-    for key, clat in reader:
-        batch.append((key, clat))
-        arcs += len(clat["arc_src"])
-        if arcs >= po["batch-arcs"]:
-            flush(batch)
-            batch, arcs = [], 0
-    flush(batch)
+    for batch in kt.batches(reader, lambda b: len(b[1]["arc_src"]), po["batch-arcs"], "after"):
+        flush(batch)
     for w in writers:
         w.close()
     den = f32(n_done) if n_done > 0 else f32(1.0)                             # :103

@@ -13,7 +13,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-scale"
 USAGE = ("Apply scaling to lattice weights\n"
          "Usage: lattice-scale [options] lattice-rspecifier lattice-wspecifier\n"
          " e.g.: lattice-scale --lm-scale=0.0 ark:1.lats ark:scaled.lats\n")
@@ -52,33 +54,18 @@ def scale_compact_lattice(scale, clat):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-scale"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    except AssertionError as e:       # KALDI_ASSERT aborts
-        sys.stderr.write("%s\n" % e)
-        return 134
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI, assert_status=134)             # KALDI_ASSERT aborts
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
-    po.register("inv-acoustic-scale", 1.0, "An alternative way of setting the acoustic scale: you can set its inverse.", float)
-    po.register("lm-scale", 1.0, "Scaling factor for graph/lm costs", float)
-    po.register("acoustic2lm-scale", 0.0, "Add this times original acoustic costs to LM costs", float)
-    po.register("lm2acoustic-scale", 0.0, "Add this times original LM costs to acoustic costs", float)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 2:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
+        po.register("inv-acoustic-scale", 1.0, "An alternative way of setting the acoustic scale: you can set its inverse.", float)
+        po.register("lm-scale", 1.0, "Scaling factor for graph/lm costs", float)
+        po.register("acoustic2lm-scale", 0.0, "Add this times original acoustic costs to LM costs", float)
+        po.register("lm2acoustic-scale", 0.0, "Add this times original LM costs to acoustic costs", float)
+    po = kt.parse(cli, PROG, USAGE, argv, register, 2)
+    if po is None:
         return 1
     reader = cli.SequentialTableReader(po.get_arg(1), "compact_lattice")
     writer = cli.TableWriter(po.get_arg(2), "compact_lattice")

@@ -27,8 +27,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from tools.lattice_mbr_decode import batches, sweep_points  # noqa: E402
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-to-ctm-conf"
 USAGE = ("This tool turns a lattice into a ctm with confidences, based on the\n"
          "posterior probabilities in the lattice.  The word sequence in the\n"
          "ctm is determined as follows.  Firstly we determine the initial word\n"
@@ -70,53 +71,40 @@ def ctm_lines(key, r, frame_shift):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-to-ctm-conf"
-    capi = importlib.import_module("old-kaldi-git_amd.capi")
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError, capi.KhError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI_KH)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
-    po.register("inv-acoustic-scale", 1.0, "An alternative way of setting the acoustic scale: you can set its inverse.", float)
-    po.register("lm-scale", 1.0, "Scaling factor for language model probabilities", float)
-    po.register("decode-mbr", True, "If true, do Minimum Bayes Risk decoding (else, Maximum a Posteriori)", bool)
-    po.register("frame-shift", 0.01, "Time in seconds between frames.", float)
-    po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
-                "--inv-acoustic-scale before the decoding, LMWT in the output name stands for it", str)
-    po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
-                "before the decoding, WIP in the output name stands for it", str)
-    po.register("batch-arcs", 200000, "[MI355X] lattice arcs per call", int)
-    po.register("gpu", 0, "[MI355X] device ordinal", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 2 and po.num_args() != 3:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
+        po.register("inv-acoustic-scale", 1.0, "An alternative way of setting the acoustic scale: you can set its inverse.", float)
+        po.register("lm-scale", 1.0, "Scaling factor for language model probabilities", float)
+        po.register("decode-mbr", True, "If true, do Minimum Bayes Risk decoding (else, Maximum a Posteriori)", bool)
+        po.register("frame-shift", 0.01, "Time in seconds between frames.", float)
+        po.register("inv-acoustic-scales", "", "[MI355X] sweep: first:last or a comma list; each value as lattice-scale "
+                    "--inv-acoustic-scale before the decoding, LMWT in the output name stands for it", str)
+        po.register("word-ins-penalties", "", "[MI355X] sweep: a comma list; each value as lattice-add-penalty --word-ins-penalty "
+                    "before the decoding, WIP in the output name stands for it", str)
+        po.register("batch-arcs", 200000, "[MI355X] lattice arcs per call", int)
+        po.register("gpu", 0, "[MI355X] device ordinal", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, range(2, 4))
+    if po is None:
         return 1
     api = importlib.import_module("old-kaldi-git_amd.api")
     one_best_rspecifier = po.get_arg(2) if po.num_args() == 3 else ""        # :86-94
     ctm_arg = po.num_args()
-    sw = sweep_points(cli, api, po, 1, ctm_arg)
+    sw = kt.score_sweep(cli, api, po, (ctm_arg,), "outputs")
     if sw is not None:
         if f32(po["acoustic-scale"]) != 1.0 or f32(po["inv-acoustic-scale"]) != 1.0 or f32(po["lm-scale"]) != 1.0:
             raise cli.KaldiError("the sweep stands for lattice-scale | lattice-add-penalty | lattice-to-ctm-conf with the last "
                                  "one's scales at 1.0: do not combine it with --acoustic-scale / --inv-acoustic-scale / --lm-scale")
-        names, points, specs = sw
+        points, specs, tag = sw
         outs = [s[0] for s in specs]
     else:
-        names = [None]
         # :80-82, :122 (score_point asserts acoustic_scale == 1.0 || inv_acoustic_scale == 1.0 and divides in float)
         points = [api.score_point(lm_scale=po["lm-scale"], acoustic_scale=po["acoustic-scale"], inv_acoustic_scale=po["inv-acoustic-scale"])]
         outs = [po.get_arg(ctm_arg)]
+        tag = lambda p: ""
     for o in outs:
         if cli.classify_wspecifier(o)[0] is not None:                        # :96-103
             raise cli.KaldiError("The output ctm file should not be a wspecifier. Please use things like 1.ctm istead of ark:-")
@@ -126,8 +114,7 @@ def run(cli, argv, prog):
     kos = [cli.open_output(o) for o in outs]                                 # :110 (text mode)
     api.select_gpu(po["gpu"])
     n_done, n_words, tot = [0] * K, [0] * K, [f32(0.0)] * K
-    tag = lambda p: "" if names[p] is None else "[LMWT=%s WIP=%s] " % names[p]
-    for batch in batches(reader, po["batch-arcs"]):
+    for batch in kt.batches(reader, lambda b: len(b[1]["arc_src"]), po["batch-arcs"], "after"):
         keep, given = [], []
         for key, clat in batch:
             if int(clat["n_states"]) == 0 or int(clat.get("start", 0)) < 0:

@@ -15,7 +15,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "lattice-to-post"
 USAGE = ("Do forward-backward and collect posteriors over lattices.\n"
          "Usage: lattice-to-post [options] lats-rspecifier posts-wspecifier [loglikes-wspecifier]\n"
          " e.g.: lattice-to-post --acoustic-scale=0.1 ark:1.lats ark:1.post\n"
@@ -61,29 +63,17 @@ def top_sorted_csr(L, lm_scale, acoustic_scale):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "lattice-to-post"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
-    po.register("lm-scale", 1.0, 'Scaling factor for "graph costs" (including LM costs)', float)
-    po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per forward-backward call", int)
-    po.register("gpu", 0, "[MI355X] device ordinal", int)
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() < 2 or po.num_args() > 3:
-        po.print_usage()
+def run(cli, argv):
+    def register(po):
+        po.register("acoustic-scale", 1.0, "Scaling factor for acoustic likelihoods", float)
+        po.register("lm-scale", 1.0, 'Scaling factor for "graph costs" (including LM costs)', float)
+        po.register("batch-arcs", 2000000, "[MI355X] lattice arcs per forward-backward call", int)
+        po.register("gpu", 0, "[MI355X] device ordinal", int)
+    po = kt.parse(cli, PROG, USAGE, argv, register, range(2, 4))
+    if po is None:
         return 1
     if po["acoustic-scale"] == 0.0:
         raise cli.KaldiError("Do not use a zero acoustic scale (cannot be inverted)")
@@ -95,8 +85,6 @@ def run(cli, argv, prog):
     tot = dict(n_done=0, like=0.0, ac=0.0, time=0.0)
 
     def flush(batch):
-        if not batch:
-            return
         res = api.lattice_forward_backward([c for _, c in batch])
         for (key, c), r in zip(batch, res):
             T = len(r["post"])
@@ -110,14 +98,9 @@ def run(cli, argv, prog):
             tot["ac"] += r["acoustic_like_sum"]
             tot["time"] += T
 
-    batch, arcs = [], 0
-    for key, L in reader:
-        batch.append((key, top_sorted_csr(L, po["lm-scale"], po["acoustic-scale"])))
-        arcs += len(L["arc_src"])
-        if arcs >= po["batch-arcs"]:
-            flush(batch)
-            batch, arcs = [], 0
-    flush(batch)
+    csrs = ((key, top_sorted_csr(L, po["lm-scale"], po["acoustic-scale"])) for key, L in reader)
+    for batch in kt.batches(csrs, lambda b: len(b[1]["arc_ilabel"]), po["batch-arcs"], "after"):
+        flush(batch)
     post_w.close()
     like_w.close()
     cli.log("Overall average log-like/frame is %g over %g frames.  Average acoustic like/frame is %g"

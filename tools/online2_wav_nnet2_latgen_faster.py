@@ -43,7 +43,9 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
+PROG = "online2-wav-nnet2-latgen-faster"
 USAGE = ("Reads in wav file(s) and simulates online decoding with neural nets\n"
          "(nnet2 setup), with optional iVector-based speaker adaptation and\n"
          "optional endpointing.  Note: some configuration values and inputs are\n"
@@ -111,25 +113,10 @@ def ivector_info(conf_path, kio, cli, online):
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    prog = "online2-wav-nnet2-latgen-faster"
-    argv = [prog] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv, prog)
-    except (cli.KaldiError, ValueError) as e:
-        sys.stderr.write("ERROR (%s) %s\n" % (prog, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI)
 
 
-def run(cli, argv, prog):
-    cli.start_pipe_helper()               # before anything initialises the GPU
-    kio = importlib.import_module("old-kaldi-git_amd.kaldi_io")
-    online2 = importlib.import_module("old-kaldi-git_amd.online2")
-    lf = importlib.import_module("tools.latgen_faster")
-    po = cli.ParseOptions(USAGE)
-    t_start = time.time()
+def register_options(po, lf, endpoint):
     po.register("chunk-length", 0.05, "Length of chunk size in seconds, that we process.  Set to <= 0 to use all input in one chunk.", float)
     po.register("word-symbol-table", "", "Symbol table for words [for debug output]")
     po.register("do-endpointing", False, "If true, apply endpoint detection")
@@ -161,24 +148,29 @@ def run(cli, argv, prog):
     po.register("pad-input", True, "If true, pad acoustic features with required acoustic context past edges of file.")
     po.register("max-nnet-batch-size", 256, "Maximum batch size we use in neural-network decodable object, in cases where we are not "
                 "constrained by currently available frames (this will rarely make a difference)", int)
-    endpoint = online2.OnlineEndpointConfig()
     endpoint.register(po)
     po.register("reference-order", True, "[MI355X] decode in LatticeFasterDecoder's own iteration order (HashList order, running next_cutoff): the lattices the "
                 "reference binary itself writes, bit for bit (the default since round 6)")
     po.register("canonical-order", False, "[MI355X] opt out of --reference-order: the order-independent acceptance rule (a cheaper kernel; same 1-best on every "
                 "recipe-like case measured, 0-6 % different raw-lattice arcs; DESIGN.md).  KH_DECODER_ORDER=reference|canonical in the "
                 "environment overrides both")
-    po.register("gpu", -1, "[MI355X] device ordinal (CuDevice::SelectGpuId); -1: LOCAL_RANK, else 0", int)
-    po.register("world", 0, "[MI355X] number of ranks sharing the job (default: WORLD_SIZE, else 1): the SPEAKERS of the spk2utt "
-                "table are dealt to the ranks longest-first (a speaker's adaptation state chains its utterances); every JOB in the "
-                "arguments becomes rank + 1", int)
-    po.register("rank", -1, "[MI355X] this process's rank (default: RANK, else 0)", int)
+    kt.register_gpu(po, "[MI355X] device ordinal (CuDevice::SelectGpuId); -1: LOCAL_RANK, else 0")
+    kt.register_ranks(po, "[MI355X] number of ranks sharing the job (default: WORLD_SIZE, else 1): the SPEAKERS of the spk2utt "
+                      "table are dealt to the ranks longest-first (a speaker's adaptation state chains its utterances); every JOB in the "
+                      "arguments becomes rank + 1")
     po.register("dry-run", False, "[MI355X] read the inputs and the shard, decode nothing (multi-rank plumbing test without a GPU)")
-    po.read(argv)
-    cli.set_program_name(prog)
-    if po.num_args() != 5:
-        po.print_usage()
+
+
+def run(cli, argv):
+    kio = importlib.import_module("old-kaldi-git_amd.kaldi_io")
+    online2 = importlib.import_module("old-kaldi-git_amd.online2")
+    lf = importlib.import_module("tools.latgen_faster")
+    endpoint = online2.OnlineEndpointConfig()
+    t_start = time.time()
+    po = kt.parse(cli, PROG, USAGE, argv, lambda po: register_options(po, lf, endpoint), 5)
+    if po is None:
         return 1
+    # the ranks: options as parsed, JOB replaced in the positional arguments only (the speakers are dealt out below)
     sharding = importlib.import_module("old-kaldi-git_amd.sharding")
     rank, world = sharding.tool_ranks(po["world"], po["rank"])
     if world > 1:
@@ -236,7 +228,7 @@ def run(cli, argv, prog):
     # ---- the GPU from here on
     import torch
     api = importlib.import_module("old-kaldi-git_amd.api")
-    api.select_gpu(po["gpu"] if po["gpu"] >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
+    kt.select_gpu(api, po)
     mfcc = api.Mfcc(**mfcc_kw)
     ivec = api.OnlineIvectorExtractor(info) if info is not None else None
     pipe = api.OnlineNnet2FeaturePipeline(mfcc, ivec)

@@ -8,6 +8,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+kt = importlib.import_module("old-kaldi-git_amd.kaldi_tool")
 
 PROG = "sum-lda-accs"
 USAGE = ("Sum stats obtained with acc-lda.\n"
@@ -15,38 +16,18 @@ USAGE = ("Sum stats obtained with acc-lda.\n"
 
 
 def main(argv=None):
-    cli = importlib.import_module("old-kaldi-git_amd.kaldi_cli")
-    argv = [PROG] + list(sys.argv[1:] if argv is None else argv)
-    try:
-        return run(cli, argv)
-    except (cli.KaldiError, ValueError) as e:     # "catch(const std::exception &e) { std::cerr << e.what(); return -1; }"
-        sys.stderr.write("ERROR (%s) %s\n" % (PROG, e))
-        return 255
-    finally:
-        cli.stop_pipe_helper()
+    return kt.run_tool(PROG, run, argv, kt.KALDI)
 
 
 def run(cli, argv):
-    cli.start_pipe_helper()
-    po = cli.ParseOptions(USAGE)
-    po.register("binary", True, "Write accumulators in binary mode.")
-    po.read(argv)
-    cli.set_program_name(PROG)
-    if po.num_args() < 2:
-        po.print_usage()
+    po = kt.parse(cli, PROG, USAGE, argv, lambda po: po.register("binary", True, "Write accumulators in binary mode."), lambda n: n >= 2)
+    if po is None:
         return 1
     kio = importlib.import_module("old-kaldi-git_amd.kaldi_io")
     acc = kio.empty_lda_accs()                        # LdaEstimate lda;
     for i in range(2, po.num_args() + 1):
         acc = cli.read_kaldi_object(po.get_arg(i), lambda s, b: kio.read_lda_accs(s, b, add_into=acc))
-    f, kind = cli.open_output(po.get_arg(1))
-    if po["binary"]:
-        f.write(b"\0B")
-    kio.write_lda_accs(f, acc, po["binary"])
-    if kind == "stdout":
-        f.flush()
-    elif f.close() not in (None, 0):
-        raise cli.KaldiError("Error closing output stream " + po.get_arg(1))
+    cli.write_kaldi_object(po.get_arg(1), po["binary"], lambda f: kio.write_lda_accs(f, acc, po["binary"]))
     return 0
 
 

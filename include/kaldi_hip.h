@@ -1443,6 +1443,34 @@ int kh_lda_max_dim(void);
  * x pairs of 64-column super tiles), passes. */
 int kh_lda_last_timings(float *ms, int32_t *counts);
 
+/* ------------------------------------------------------------------ tree statistics (csrc/kh_tree.hip)
+ * acc-tree-stats for a batch of stacked frames: GaussClusterable::AddStats(row, 1.0) (tree/clusterable-classes.cc:137-142)
+ * for every frame whose event the caller has worked out (AccumulateTreeStats, hmm/tree-accu.cc:56-104).  feats (DEVICE, T x
+ * D, row pitch feat_stride); frame_event (HOST, T entries): the frame's event 0 ... num_events - 1, or -1 for a frame that is
+ * not used.  HOST outputs count [num_events] and stats [num_events x 2 x D] (an event's first-order row, then its
+ * second-order row).  For every event e and column d, from the incoming value (add != 0) or from zero (add == 0: the
+ * buffers are overwritten), over the frames with frame_event[t] == e in ascending t, x = feats[t][d]:
+ *     stats[e][0][d] += (double)x,   stats[e][1][d] += (double)(float)(x * x)
+ * - the product rounded to float and then widened, as AddVec2's alpha == 1.0 branch has it, never fused with the add - and
+ * count[e] becomes its prior value (or zero) plus the number of those frames, which is exact below 2^53.  One chain of double
+ * adds per (event, column), never cut into partial sums, no atomics: the result is bit-equal to the reference's loop, and a
+ * job gives the same bits however it is cut into calls that run on from one another with add.  An event without a frame keeps
+ * what it holds under add and is zero without.  COST: stats travels whole - all num_events rows go up under add and all come
+ * back, events without a frame included (16 D bytes per event each way) - so give the call the events the frames touch, as
+ * api.TreeStats does, not a job's whole table.  (Moving only the touched rows was built and measured: packing and unpacking
+ * them on the host cost more than the bytes it saved at two thirds of the events touched.)  T = 0 and num_events = 0 are valid.  D = 1 ... kh_tree_max_dim (512).
+ * Before any launch, KH_EINVAL naming the offender: D outside that range, feat_stride below D, a frame whose event lies
+ * outside -1 ... num_events - 1. */
+int kh_tree_acc_stats(const float *feats, int T, int D, int feat_stride, const int32_t *frame_event, int num_events, int add,
+                      double *count, double *stats);
+int kh_tree_max_dim(void);
+/* Rows of an event's run staged per step (the tests' edge counts: runs of tile - 1, tile, tile + 1 frames). */
+int kh_tree_tile(void);
+/* ms[3]: milliseconds of the calling thread's last kh_tree_acc_stats: the whole call, its host plan (check, counting sort by
+ * event, work list), its kernel alone (device events).  counts[4]: frames with an event, events with a frame, work items
+ * (one wave per event with a frame and block of 64 columns), frames of the longest event. */
+int kh_tree_last_timings(float *ms, int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3758,6 +3758,234 @@ def add_lda_stats(into, acc):
         raise KhError(str(e))
 
 
+# ---------------------------------------------------------------- tree statistics (csrc/kh_tree.hip)
+# acc-tree-stats for stacked frames.  An event (EventType) is a tuple of (key, value) pairs sorted by key: key -1 (kPdfClass)
+# with the frame's pdf-class, key j with the phone at position j of the context window.
+def tree_acc_stats(feats, frame_event, count, stats, add=True):
+    """GaussClusterable::AddStats(row, 1.0) for every frame with an event (kh_tree_acc_stats): one library call.  feats: 2-D
+    float32 device tensor of at most tree_max_dim() columns; frame_event [T] int32, -1 = frame not used; count [E] and stats
+    [E, 2, D]: contiguous float64 host arrays, run on from (add) or overwritten.  Bit-equal to the reference's loop."""
+    if feats.dim() == 2 and feats.shape[0] == 0 and feats.dtype == torch.float32 and feats.is_cuda:
+        T, D, stride = 0, int(feats.shape[1]), int(feats.shape[1])            # no rows: the strides of an empty tensor say nothing
+    else:
+        T, D, stride = _feat_args(feats)
+    fe = np.ascontiguousarray(frame_event, np.int32).reshape(-1)
+    if len(fe) != T:
+        raise KhError("tree_acc_stats: %d frame events against %d frames" % (len(fe), T))
+    E = len(count)
+    for name, a, shape in (("count", count, (E,)), ("stats", stats, (E, 2, D))):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous or a.shape != shape:
+            raise KhError("tree_acc_stats: %s must be a contiguous float64 array of shape %r" % (name, shape))
+    dp = capi.c_double_p
+    check(lib().kh_tree_acc_stats(_p(feats), T, D, stride, fe.ctypes.data_as(capi.c_int32_p), E, 1 if add else 0, count.ctypes.data_as(dp),
+                                  stats.ctypes.data_as(dp)))
+
+
+def tree_max_dim():
+    return int(lib().kh_tree_max_dim())
+
+
+def tree_tile():
+    """Rows of an event's run staged per step (kTile of csrc/kh_tree.hip)."""
+    return int(lib().kh_tree_tile())
+
+
+def tree_last_timings():
+    """The calling thread's last tree_acc_stats: milliseconds of the call, its host plan and its kernel; frames with an event,
+    events with a frame, work items (waves), frames of the longest event."""
+    return _timings(lib().kh_tree_last_timings, ("call_ms", "plan_ms", "kernels_ms"), ("frames", "events", "work_items", "longest"))
+
+
+def tree_stats_ci_phones(text):
+    """The --ci-phones string of acc-tree-stats (bin/acc-tree-stats.cc:80-87): colon-separated integers, sorted; a repeated
+    phone or phone 0 is the binary's error."""
+    if text == "":
+        return []
+    try:
+        phones = sorted(int(w) for w in text.split(":"))
+    except ValueError:
+        raise KhError("Invalid set of ci_phones: " + text)
+    if any(a == b for a, b in zip(phones, phones[1:])) or phones[0] == 0:
+        raise KhError("Invalid set of ci_phones: " + text)
+    return phones
+
+
+def tree_stats_tables(tmodel):
+    """What tree_stats_frame_events looks up per transition-id, beside read_transition_model's tables: the transition-state,
+    the pdf-class of its HMM-state (TransitionIdToPdfClass), and per phone the pdf-class of the topology entry's state 0."""
+    topo = tmodel["topo"]
+    pdf_class = [-1]
+    for phone, hmm_state, _ in np.asarray(tmodel["triples"]).reshape(-1, 3):
+        entry = topo["entries"][topo["phone2idx"][int(phone)]]
+        pdf_class += [int(entry[int(hmm_state)][0])] * len(entry[int(hmm_state)][1])
+    first = np.full(len(topo["phone2idx"]), -1, np.int32)
+    for ph in topo["phones"]:
+        first[ph] = topo["entries"][topo["phone2idx"][ph]][0][0]
+    return dict(tid2state=transition_id_to_state(tmodel), tid2pdf_class=np.asarray(pdf_class, np.int32), phone_first_pdf_class=first)
+
+
+def _split_to_phones(tmodel, tables, ali):
+    """SplitToPhones (hmm/hmm-utils.cc:594-701) on a non-empty alignment -> (was_ok, the phone instances' end points)."""
+    n = len(ali)
+    tstate, phone = tables["tid2state"][ali], tmodel["tid2phone"][ali]
+    loop, final = tmodel["tid_is_self_loop"][ali], tmodel["tid_is_final"][ali]
+    # IsReordered: the first change of transition-state with a self-loop on either side decides
+    change = np.nonzero(tstate[:-1] != tstate[1:])[0]
+    decided = change[loop[change] | loop[change + 1]]
+    if len(decided):
+        i = int(decided[0])
+        if loop[i] and loop[i + 1]:
+            raise KhError("KALDI_ASSERT: at IsReordered:hmm-utils.cc:602, failed: !(is_loop_1 && is_loop_2)")
+        reordered = bool(loop[i])
+    else:
+        reordered = bool(not loop[0] and loop[-1])
+    # SplitToPhonesInternal.  Reordered: the self-loops that follow a final transition-id belong to its phone and are stepped
+    # over without being looked at.
+    skipped = np.zeros(n, bool)
+    if reordered:
+        last_other = np.maximum.accumulate(np.where(~loop, np.arange(n), -1))      # the last position <= i that is no self-loop
+        skipped = loop & (last_other >= 0) & final[np.maximum(last_other, 0)]
+        bad = np.nonzero(skipped & (tstate != np.concatenate([[0], tstate[:-1]])))[0]
+        if len(bad):
+            raise KhError("KALDI_ASSERT: at SplitToPhonesInternal:hmm-utils.cc:645, failed: trans_model.TransitionIdToTransitionState("
+                          "alignment[i]) == trans_model.TransitionIdToTransitionState(alignment[i+1])")
+    nxt_state = np.concatenate([tstate[1:], [0]])
+    nxt_phone = np.concatenate([phone[1:], [0]])
+    last = np.arange(n) == n - 1
+    error_end = ~final & (last | ((tstate != nxt_state) & (phone != nxt_phone)))   # an end the IsFinal check should have found
+    looked_at = ~skipped
+    is_end = looked_at & (final | error_end)
+    was_ok = not bool((looked_at & error_end).any())
+    # an end point is one past the position, or past the self-loops stepped over after it
+    after = np.minimum.accumulate(np.where(looked_at, np.arange(n), n)[::-1])[::-1]   # the first looked-at position >= i
+    after = np.concatenate([after[1:], [n]])
+    ends = after[np.nonzero(is_end)[0]]
+    starts = np.concatenate([[0], ends[:-1]])
+    first_tid = ali[starts]
+    emitting = tables["phone_first_pdf_class"][tmodel["tid2phone"][first_tid]] != -1
+    if bool((emitting & (tmodel["tid2hmm_state"][first_tid] != 0)).any()):
+        was_ok = False
+    return was_ok, starts, ends
+
+
+def tree_stats_frame_events(tmodel, alignment, N=3, P=1, ci_phones=(), phone_map=None, tables=None, codes=False):
+    """The events of AccumulateTreeStats (hmm/tree-accu.cc:36-106) for one alignment -> (ok, events): ok False when
+    SplitToPhones finds the alignment bad (the utterance then contributes nothing), else events[t] is the event of frame t.
+    The alignment is cut into phone instances (SplitToPhones with IsReordered, hmm/hmm-utils.cc:594-701); an instance's event
+    holds key j = 0 ... N - 1 with the phone at window position j around central position P - 0 outside the utterance, the
+    phones through phone_map first - but only key P when the mapped central phone is one of ci_phones; each frame adds key -1
+    (kPdfClass) with TransitionIdToPdfClass, and the pairs are sorted.  ci_phones: sorted and unique (tree_stats_ci_phones);
+    phone_map: int array indexed by phone (kaldi_io.read_phone_map) or None; tables: tree_stats_tables(tmodel), made here
+    when absent.  N and P of any sign are what the reference's loops make of them (a window that does not meet every phone
+    instance once is its cur_pos assertion; N <= 0 keeps no phone key).  The work is per phone instance; a frame costs one
+    list index.  codes=True -> (ok, table, code): the distinct (instance, pdf-class) events of the utterance and per frame
+    its index into them (int32), events[t] = table[code[t]] - what TreeStats.accumulate(codes=...) takes without touching a
+    tuple per frame.  Raises KhError with the reference's message where it asserts or errors."""
+    ci = [int(p) for p in ci_phones]
+    if any(a >= b for a, b in zip(ci, ci[1:])):
+        raise KhError("KALDI_ASSERT: at AccumulateTreeStats:tree-accu.cc:46, failed: IsSortedAndUniq(ci_phones)")
+    ali = np.asarray(alignment, np.int64).reshape(-1)
+    if len(ali) == 0:
+        return (True, [], np.zeros(0, np.int32)) if codes else (True, [])
+    n_tids = len(tmodel["tid2pdf"]) - 1
+    if ali.min() < 1 or ali.max() > n_tids:
+        raise KhError("transition-id %d, the model has 1 .. %d" % (int(ali.max() if ali.min() >= 1 else ali.min()), n_tids))
+    if tables is None:
+        tables = tree_stats_tables(tmodel)
+    ok, starts, ends = _split_to_phones(tmodel, tables, ali)
+    if not ok:
+        return (False, [], np.zeros(0, np.int32)) if codes else (False, [])
+    L = len(starts)
+    phones = tmodel["tid2phone"][ali[starts]].astype(np.int64)
+    if phone_map is not None:                                 # MapPhone: 0 stays, out of range is the reference's error
+        pm = np.asarray(phone_map, np.int64)
+        out = np.nonzero((phones != 0) & ((phones < 0) | (phones >= len(pm))))[0]
+        if len(out):
+            raise KhError("Out-of-range phone %d bad --phone-map option?" % int(phones[out[0]]))
+        phones = np.where(phones == 0, 0, pm[np.clip(phones, 0, len(pm) - 1)])
+    # the windows i = -N ... L - 1 with their central instance i + P inside the utterance, in order: every instance must be
+    # met exactly once (cur_pos runs through the alignment)
+    centres = [i + P for i in range(-N, L) if 0 <= i + P < L]
+    if centres != list(range(L)):
+        raise KhError("KALDI_ASSERT: at AccumulateTreeStats:tree-accu.cc:105, failed: cur_pos == static_cast<int>(alignment.size())")
+    padded = np.concatenate([np.zeros(max(N, 0) + abs(P), np.int64), phones, np.zeros(max(N, 0) + abs(P), np.int64)])
+    base = max(N, 0) + abs(P) - P                             # instance c's window position j is padded[base + c + j]
+    ci_set = set(ci)
+    pdf_class = tables["tid2pdf_class"][ali]
+    table, code = [], np.empty(len(ali), np.int64)
+    for c in range(L):
+        s, e = int(starts[c]), int(ends[c])
+        window = padded[base + c:base + c + N].tolist()
+        ctx_dep = int(phones[c]) not in ci_set
+        context = tuple((j, window[j]) for j in range(N) if ctx_dep or j == P)
+        classes, inverse = np.unique(pdf_class[s:e], return_inverse=True)
+        code[s:e] = len(table) + inverse
+        table += [tuple(sorted(context + ((-1, int(pc)),))) for pc in classes]
+    if codes:
+        return True, table, code.astype(np.int32)
+    return True, [table[k] for k in code.tolist()]
+
+
+class TreeStats:
+    """The running statistics of acc-tree-stats: std::map<EventType, GaussClusterable*> as a host table of float64 rows that
+    the library runs on from, batch after batch."""
+
+    def __init__(self, dim, var_floor=0.01):
+        self.dim = int(dim)
+        self.var_floor = float(np.float32(var_floor))         # var_floor_ is a double that holds the float option
+        self._row = {}
+        self._count = np.zeros(0, np.float64)                 # the table's capacity: it doubles, len(self._row) rows are in use
+        self._stats = np.zeros((0, 2, self.dim), np.float64)
+
+    def __len__(self):
+        return len(self._row)
+
+    def accumulate(self, feats, frame_events, codes=None):
+        """feats: 2-D float32 device tensor [T, dim]; frame_events: T events (tree_stats_frame_events), None for a frame
+        that is not used.  With codes - int array [T], -1 for a frame that is not used - frame_events is instead a table of
+        events (repeats allowed) and frame t has the event frame_events[codes[t]] (tree_stats_frame_events(codes=True), the
+        utterances' tables joined): Python then works per table entry, not per frame.  The events the batch touches get
+        local ids, their rows of the host table are gathered, ONE tree_acc_stats call runs on from them, and the rows are
+        put back."""
+        T = int(feats.shape[0])
+        if int(feats.shape[1]) != self.dim:
+            raise KhError("TreeStats.accumulate: features of dimension %d, the statistics have %d" % (int(feats.shape[1]), self.dim))
+        local = {}
+        if codes is None:
+            if len(frame_events) != T:
+                raise KhError("TreeStats.accumulate: %d frame events against %d frames" % (len(frame_events), T))
+            fe = np.asarray([-1 if ev is None else local.setdefault(ev, len(local)) for ev in frame_events], np.int32)
+        else:
+            codes = np.asarray(codes, np.int64).reshape(-1)
+            if len(codes) != T:
+                raise KhError("TreeStats.accumulate: %d frame events against %d frames" % (len(codes), T))
+            if len(codes) and (codes.min() < -1 or codes.max() >= len(frame_events)):
+                raise KhError("TreeStats.accumulate: a code outside -1 ... %d" % (len(frame_events) - 1))
+            met = np.unique(codes[codes >= 0])                # a table entry no frame names does not become an event
+            of_entry = np.full(len(frame_events) + 1, -1, np.int32)          # [-1] serves the frames that are not used
+            of_entry[met] = [local.setdefault(frame_events[k], len(local)) for k in met.tolist()]
+            fe = of_entry[codes]
+        new = [ev for ev in local if ev not in self._row]
+        if new:
+            need = len(self._row) + len(new)
+            if need > len(self._count):
+                room = max(need, 2 * len(self._count), 1024)
+                self._count = np.concatenate([self._count, np.zeros(room - len(self._count), np.float64)])
+                self._stats = np.concatenate([self._stats, np.zeros((room - len(self._stats), 2, self.dim), np.float64)])
+            for ev in new:
+                self._row[ev] = len(self._row)
+        rows = np.asarray([self._row[ev] for ev in local], np.int64)
+        count, stats = np.ascontiguousarray(self._count[rows]), np.ascontiguousarray(self._stats[rows])
+        tree_acc_stats(feats, fe, count, stats, add=True)
+        self._count[rows], self._stats[rows] = count, stats
+
+    def items(self):
+        """(event, dict(count, var_floor, stats [2, dim])) in std::map<EventType> order: the pairs compared in turn."""
+        for ev in sorted(self._row):
+            r = self._row[ev]
+            yield ev, dict(count=float(self._count[r]), var_floor=self.var_floor, stats=self._stats[r])
+
+
 # ---- host posterior / transform algebra of the fMLLR recipes
 def weight_silence_post(tid2phone, silence_phones, silence_scale, post, distribute=False):
     """WeightSilencePost / WeightSilencePostDistributed (hmm/posterior.cc:361-413): tid2phone indexed by transition-id."""

@@ -278,6 +278,10 @@ SIGNATURES = {
     "kh_lda_max_slices": (C.c_int, []),
     "kh_lda_max_dim": (C.c_int, []),
     "kh_lda_last_timings": (C.c_int, [c_float_p, c_int32_p]),
+    "kh_tree_acc_stats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_int, C.c_int, c_double_p, c_double_p]),
+    "kh_tree_max_dim": (C.c_int, []),
+    "kh_tree_tile": (C.c_int, []),
+    "kh_tree_last_timings": (C.c_int, [c_float_p, c_int32_p]),
     "kh_lattice_forward_backward_mpe": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, c_int32_p, C.c_int, C.c_int, c_float_p, c_double_p, c_int32_p]),
     "kh_rescore_lattice": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, vp, C.c_int, c_int32_p, vp]),
     "kh_merge_pair_vector_summing": (C.c_int, [i64, c_int32_p, c_int32_p, c_float_p, i32, c_int32_p, c_int32_p, c_float_p, c_int64_p]),

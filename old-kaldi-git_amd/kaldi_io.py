@@ -2113,3 +2113,115 @@ def read_lda_accs(s, binary=True, add_into=None):
             raise ValueError("Unexpected token '%s' in file " % tok)
         tok = read_token(s, binary)
     return acc if add_into is None else add_lda_accs(add_into, acc)
+
+
+# ---------------------------------------------------------------- tree statistics (the .treeacc files of acc-tree-stats)
+# BuildTreeStatsType as a list of (event, clusterable): event a tuple of (key, value) pairs (EventType), clusterable
+# dict(count float, var_floor float - the double that holds the float option -, stats [2, D] float64), or None for a NULL pointer.
+def _write_uint32(f, binary, v):
+    """WriteBasicType<uint32> (io-funcs-inl.h:32-50): the size byte of an unsigned type is negative."""
+    f.write(b"\xfc" + struct.pack("<I", int(v)) if binary else b"%d " % int(v))
+
+
+def _read_uint32(s, binary):
+    if binary:
+        n = s.get()[0]
+        if n != 0xfc:
+            raise ValueError("ReadBasicType: did not get expected integer type, %d vs. -4.  You can change this code to successfully"
+                             " read it later, if needed." % (n - 256 if n > 127 else n))
+        return struct.unpack("<I", s.get(4))[0]
+    return int(_text_word(s))
+
+
+def _write_double_g(f, binary, v):
+    """WriteBasicType<double>: in text `os << f << " "` at the stream's 7 digits."""
+    f.write(b"\x08" + struct.pack("<d", float(v)) if binary else (_fmt(v) + " ").encode())
+
+
+def write_event_type(f, binary, event):
+    """WriteEventType (tree/event-map.cc:228-237)."""
+    write_token(f, binary, "EV")
+    _write_uint32(f, binary, len(event))
+    for k, v in event:
+        write_int32(f, binary, k)
+        write_int32(f, binary, v)
+    if not binary:
+        f.write(b"\n")
+
+
+def read_event_type(s, binary):
+    """ReadEventType (tree/event-map.cc:239-249) -> a tuple of (key, value) pairs."""
+    expect_token(s, binary, "EV")
+    n = _read_uint32(s, binary)
+    return tuple((read_int32(s, binary), read_int32(s, binary)) for _ in range(n))
+
+
+def write_tree_stats(f, stats, binary=True):
+    """WriteBuildTreeStats (tree/build-tree-utils.cc:29-43) over GaussClusterable::Write (tree/clusterable-classes.cc:173-178):
+    the events in the order given (the tools pass std::map<EventType> order)."""
+    write_token(f, binary, "BTS")
+    _write_uint32(f, binary, len(stats))
+    for event, gc in stats:
+        write_event_type(f, binary, event)
+        f.write((b"T" if gc is not None else b"F") + (b"" if binary else b" "))
+        if gc is not None:
+            write_token(f, binary, "GCL")
+            _write_double_g(f, binary, gc["count"])
+            _write_double_g(f, binary, gc["var_floor"])
+            write_matrix(f, np.asarray(gc["stats"], np.float64), binary)
+    if not binary:
+        f.write(b"\n")
+
+
+def read_tree_stats(s, binary=True):
+    """ReadBuildTreeStats (tree/build-tree-utils.cc:46-60) with a GaussClusterable example -> [(event, clusterable or None)]."""
+    s = _as_stream(s)
+    expect_token(s, binary, "BTS")
+    out = []
+    for _ in range(_read_uint32(s, binary)):
+        event = read_event_type(s, binary)
+        if not read_bool(s, binary):
+            out.append((event, None))
+            continue
+        expect_token(s, binary, "GCL")
+        count, var_floor = read_double(s, binary), read_double(s, binary)
+        if binary:
+            m = read_matrix(s, True).astype(np.float64)
+        else:                                                 # Matrix<double>::Read in text: the words as doubles
+            s.skip_ws()
+            if s.get() != b"[":
+                raise ValueError("Expected \"[\" at the start of a text matrix")
+            rows = _read_text_rows(s)
+            if len({len(r) for r in rows}) > 1:
+                raise ValueError("Matrix has inconsistent #cols")
+            m = np.asarray(rows, np.float64).reshape(len(rows), len(rows[0]) if rows else 0)
+        out.append((event, dict(count=count, var_floor=var_floor, stats=m)))
+    return out
+
+
+def read_phone_map(f, name="standard input"):
+    """ReadPhoneMap (hmm/tree-accu.cc:109-138) over ReadIntegerVectorVectorSimple: text lines "old-phone new-phone" ->
+    int32 [max old phone + 1], -1 where nothing maps.  f: a binary stream or the bytes; name: PrintableRxfilename for the
+    messages."""
+    data = f if isinstance(f, (bytes, bytearray)) else f.read()
+    lines = data.decode("latin-1").split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()                                           # std::getline: a final newline ends the last line
+    vec = []
+    for line in lines:
+        try:
+            vec.append([int(w) for w in line.replace("\t", " ").replace("\r", " ").split(" ") if w != ""])
+        except ValueError:
+            raise ValueError("Error reading phone map from " + name)
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in vec[-1]):
+            raise ValueError("Error reading phone map from " + name)
+    phone_map = []
+    for i, v in enumerate(vec):
+        if len(v) != 2 or v[0] <= 0 or v[1] <= 0 or (v[0] < len(phone_map) and phone_map[v[0]] != -1):
+            raise ValueError("Error reading phone map from %s (bad line %d)" % (name, i))
+        if v[0] >= len(phone_map):
+            phone_map += [-1] * (v[0] + 1 - len(phone_map))
+        phone_map[v[0]] = v[1]
+    if not phone_map:
+        raise ValueError("Read empty phone map from " + name)
+    return np.asarray(phone_map, np.int32)

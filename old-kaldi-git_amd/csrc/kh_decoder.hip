@@ -4614,6 +4614,22 @@ __device__ void PruneActiveTokens(const Utt &u, const Params &p, int cur, float 
 // costs no memory access), and appends the survivors to the slot's survivor lists.  Same float operations and the
 // same unique fixed point as PruneForwardLinks (rule P).  Frames beyond kFinalDense tokens, or with more survivors
 // than the map holds, go through the general routines and global memory.
+//
+// What a dense visit reads, and when (round 8; DESIGN 3.4 has the stamps it rests on).  Destination first: of the
+// emitting link slots only link_dst is swept - 16 bytes per lane, eight slots per lane and round - and asked against a
+// BIT per token of frame f + 1 that says whether the map holds it (one LDS read per slot, no probe loop: the visit is
+// bound by the instructions its sixteen waves issue next to the other workgroup of the CU, not by its bytes or its round
+// trips).  A slot whose bit is set is listed in LDS; behind one barrier the listed slots are taken one per lane: they
+// probe the map and read link_src, link_k and tok_cost[dst], requested together.  The visit's chain: the destinations
+// of the first round were requested by the visit BEFORE (after its own sweep, so that they arrive under its barriers;
+// the frames' bounds are fetched two visits ahead for that; never for a frame that takes the general route), the
+// epsilon links' three words are requested behind the sweep and arrive under the listed slots' round trip, which is
+// the one dependent round trip of the visit (a wave that handled its own survivors made one per survivor of its
+// busiest lane, and the other fifteen waited for it at the next barrier: 5 k of the visit's 24 k cycles).
+// The survivor lists are appended to with LDS atomics in whatever order the waves arrive, before and after this change:
+// ExportSurvivors copies them by list position and the host orders a lattice's states by (frame, state) and a state's
+// arcs by all their fields (BuildLattice in kh_decoder_host.hip; ComputeBestPathLean breaks its ties on the same keys),
+// so nothing downstream sees the order.
 constexpr int kFinalDense = kLdsSlots + kLdsSlots / 2;   // 12288 extra_costs: the table's value array + half of its key array
 constexpr int kMapSlots = 2048;                          // the other half: 2048 keys + 2048 values
 constexpr int kMapMax = 1400;
@@ -4630,6 +4646,26 @@ __device__ __forceinline__ void SurvAddLink(const Utt &u, Blk &sh, int l, int f)
   else sh->status = 7;
 }
 
+// link_dst of the four slots from l0 of a link block that ends at `me`, in one 16-byte non-temporal access (the
+// utterance's last pass over its links); -1 for the slots at and beyond the end, which are not read.
+__device__ __forceinline__ KhInt4 LoadDst4(const Utt &u, int l0, int me) {
+  KhInt4 d = {-1, -1, -1, -1};
+  if (l0 + 4 <= me) {
+    d = Load4I_NT(u.link_dst, l0);
+  } else if (l0 < me) {
+    d.x = u.link_dst[l0];
+    if (l0 + 1 < me) d.y = u.link_dst[l0 + 1];
+    if (l0 + 2 < me) d.z = u.link_dst[l0 + 2];
+  }
+  return d;
+}
+
+// (-DKH_X_STAMPS builds: the dense visit's fine stamps 50-57 count from the visit's start)
+#ifdef KH_X_STAMPS
+#define FBS0() do { if (prof) sh->t_sub = static_cast<long long>(__builtin_amdgcn_s_memtime()); } while (0)
+#else
+#define FBS0() do {} while (0)
+#endif
 __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb, int fe, Blk &sh) {
   // the pass's own copies of the pointers it uses (see ProcessEmitting: kept in scalar registers for its duration)
   Utt u = u_in;
@@ -4644,6 +4680,17 @@ __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb
   auto mk = reinterpret_cast<__attribute__((address_space(3))) uint32_t *>(&sh->ex_ab[0]);   // key: token index within its frame + 1; 0 = empty
   auto mv = reinterpret_cast<__attribute__((address_space(3))) float *>(&sh->ex_tok[0]);
   auto map_slot = [](uint32_t i) { return (i * 0x9E3779B1u) >> 21; };
+  // which tokens of frame f + 1 the map holds, a bit per token: what a sweep asks of every link slot (one LDS read, no
+  // probe loop).  Word kFinalDense / 32 stays zero: where an excised slot's -1 and a slot beyond the block's end look.
+  // (Over the expansion sweeps' owner rows, which every sweep starts by clearing: OwnerScanInit.)
+  auto mb_bits = reinterpret_cast<__attribute__((address_space(3))) uint32_t *>(&sh->own[0][0]);
+  constexpr int kMapBitWords = kFinalDense / 32 + 1;
+  static_assert(kFinalDense % 32 == 0 && kMapBitWords <= NW * 64 && kMapBitWords <= NT, "the bit array fits the owner rows, a word per lane");
+  // ... and behind it the list of a sweep's surviving link slots: a counter and ((slot - block begin) << 14 | dst - b1)
+  auto sl_n = reinterpret_cast<__attribute__((address_space(3))) int *>(mb_bits + kMapBitWords);
+  auto sl_e = mb_bits + kMapBitWords + 1;
+  constexpr int kSweepList = NW * 64 - kMapBitWords - 1;
+  static_assert(kSweepList >= 512, "room for a frame's surviving links (27 on average)");
   const bool prof = u.phase_cycles != nullptr && t == 0;
   const int conv_upto = Uni(sh->conv_upto);
   // ---- the last frame (PruneForwardLinksFinal has run: extra_costs in memory, epsilon links excised)
@@ -4653,13 +4700,20 @@ __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb
     if (u.link_dst[l] >= 0) SurvAddLink(u, sh, l, last);
   bool nx_global = true;   // extra_costs of frame f + 1: in tok_extra (true) or in the LDS map (false)
   int b1 = fb, e1 = fe;
-  // bounds of the frame to visit, fetched one visit ahead
-  int vb = 0, ve = 0, vmb = 0, vme = 0, vnb = 0, vne = 0;
+  // bounds of the frame to visit (v*) and of the one below it (w*), fetched two visits ahead: visit f knows frame
+  // f - 1's link block early enough to request its link_dst words before its own epsilon fixed point
+  int vb = 0, ve = 0, vmb = 0, vme = 0, vnb = 0, vne = 0, wb = 0, we = 0, wmb = 0, wme = 0, wnb = 0, wne = 0;
   if (last > 0) { vb = u.frame_b[last - 1]; ve = u.frame_e[last - 1]; vmb = u.femit_b[last - 1]; vme = u.femit_e[last - 1]; vnb = u.feps_b[last - 1]; vne = u.feps_e[last - 1]; }
+  if (last > 1) { wb = u.frame_b[last - 2]; we = u.frame_e[last - 2]; wmb = u.femit_b[last - 2]; wme = u.femit_e[last - 2]; wnb = u.feps_b[last - 2]; wne = u.feps_e[last - 2]; }
+  // link_dst of the first kFinalPre slots per lane of the frame to visit, requested by the visit before (have_pre)
+  const KhInt4 none4 = {-1, -1, -1, -1};
+  KhInt4 p0 = none4, p1 = none4;
+  bool have_pre = false;
   KhSync();
   for (int f = last - 1; f >= 0; f--) {
     const int b = Uni(vb), e = Uni(ve), mb = Uni(vmb), me = Uni(vme), nb = Uni(vnb), ne = Uni(vne);
-    if (f > 0) { vb = u.frame_b[f - 1]; ve = u.frame_e[f - 1]; vmb = u.femit_b[f - 1]; vme = u.femit_e[f - 1]; vnb = u.feps_b[f - 1]; vne = u.feps_e[f - 1]; }
+    vb = wb; ve = we; vmb = wmb; vme = wme; vnb = wnb; vne = wne;
+    if (f > 1) { wb = u.frame_b[f - 2]; we = u.frame_e[f - 2]; wmb = u.femit_b[f - 2]; wme = u.femit_e[f - 2]; wnb = u.feps_b[f - 2]; wne = u.feps_e[f - 2]; }
     const int n = e - b;
     const bool fresh = f >= conv_upto;  // the frame's emitting links still carry tot_cost in link_k
     if (n > kFinalDense) {
@@ -4677,70 +4731,115 @@ __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb
       if (t == 0) sh->sched[2] += 1;
       nx_global = true;
       b1 = b; e1 = e;
+      have_pre = false;   // (nothing was requested for this frame, and nothing is for the one below it)
+      p0 = none4; p1 = none4;
       KhSync();
       continue;
     }
     if (t == 0) sh->sched[1] += 1;
+    FBS0();
+    // ---- the emitting links' destinations, unless the visit before has requested them (the bounds of frame f - 2 are
+    // on their way since the top of the loop)
+    constexpr int kBU = 4;         // a lane owns 4 consecutive link slots: one 16-byte access
+    constexpr int kFinalPre = 2;   // ... and kFinalPre such groups per round: 8192 slots, the typical frame in one round
+    KhInt4 d0 = p0, d1 = p1;
+    if (!have_pre) { d0 = LoadDst4(u, mb + t * kBU, me); d1 = LoadDst4(u, mb + (NT + t) * kBU, me); }
     for (int i = t; i < n; i += NT) *x(i) = kEncInf;
+    if (t == 0) *sl_n = 0;
     LdsSync();
-    // ---- emitting links (to frame f + 1, whose extra_costs are final): :309-323
-    constexpr int kBU = 4;   // a lane owns 4 consecutive link slots: one 16-byte access per array
-    for (int l0 = mb + t * kBU; l0 < me; l0 += NT * kBU) {
-      int dst[kBU], src[kBU];
-      float kk[kBU];
-      if (l0 + kBU <= me) {
-        const KhInt4 d4 = Load4I_NT(u.link_dst, l0), s4 = Load4I_NT(u.link_src, l0);   // (the utterance's last pass over its links)
-        const KhFloat4 k4 = Load4F_NT(u.link_k, l0);
-        dst[0] = d4.x; dst[1] = d4.y; dst[2] = d4.z; dst[3] = d4.w;
-        src[0] = s4.x; src[1] = s4.y; src[2] = s4.z; src[3] = s4.w;
-        kk[0] = k4.x; kk[1] = k4.y; kk[2] = k4.z; kk[3] = k4.w;
-      } else {
-#pragma unroll
-        for (int k = 0; k < kBU; k++) {
-          const int l = min(l0 + k, me - 1);
-          dst[k] = l0 + k < me ? u.link_dst[l] : -1; src[k] = u.link_src[l]; kk[k] = u.link_k[l];
-        }
-      }
-      float nx[kBU];
+    XS(50);
+    // A surviving link's part of :309-323: link_src, link_k, tok_cost[dst] and (through memory) the extra_cost
+    // requested together, then exactly the float operations of PruneForwardLinks.
+    auto survive = [&](int l, int dst) {
+      const int src = u.link_src[l];
+      float kk = u.link_k[l];
+      float nx = inf;
       if (nx_global) {
-#pragma unroll
-        for (int k = 0; k < kBU; k++) nx[k] = dst[k] >= 0 ? LoadExtra(&u.tok_extra[dst[k]]) : inf;
+        nx = LoadExtra(&u.tok_extra[dst]);
       } else {
-#pragma unroll
-        for (int k = 0; k < kBU; k++) {
-          nx[k] = inf;
-          if (dst[k] < 0) continue;
-          const uint32_t key = static_cast<uint32_t>(dst[k] - b1) + 1u;
-          uint32_t sl = map_slot(key);
-          for (;;) {
-            const uint32_t seen = mk[sl];
-            if (seen == key) { nx[k] = mv[sl]; break; }
-            if (seen == 0u) break;
-            sl = (sl + 1) & (kMapSlots - 1);
-          }
-        }
+        const uint32_t key = static_cast<uint32_t>(dst - b1) + 1u;
+        uint32_t sl = map_slot(key);
+        while (mk[sl] != key) sl = (sl + 1) & (kMapSlots - 1);   // (it is there: its bit is set)
+        nx = mv[sl];
       }
+      // first visit: link_k still holds the candidate's tot_cost (:309-311's parenthesis = tot_cost - cost[dst])
+      if (fresh) kk = kk - Dec(LoadCostEnc(&u.tok_cost[dst]));
+      float lec = nx + kk;
+      if (lec > lb) return;
+      if (lec < 0.0f) lec = 0.0f;
+      __hip_atomic_fetch_min(x(src - b), Enc(lec), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      SurvAddLink(u, sh, l, f);
+    };
+    // ---- emitting links (to frame f + 1, whose extra_costs are final).  Destination first: a slot whose destination
+    // has no finite extra_cost (99.7 % of them: not in the hand-off map) is dead, and its link_src and link_k are never
+    // read.  The others (27 of a frame's 8000 slots) are LISTED in LDS, slot and destination packed in a word, and taken
+    // one per lane behind a barrier: one dependent round trip for the workgroup, where a wave that handled its own made
+    // one per survivor of its busiest lane while the other waves waited at the next barrier.
+    for (int base = mb;;) {
+      const int dd[kBU * kFinalPre] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+      uint32_t hit = 0u;   // bit k: slot k's destination has a finite extra_cost
+      if (nx_global) {
+        float nx[kBU * kFinalPre];
 #pragma unroll
-      for (int k = 0; k < kBU; k++) {
-        if (nx[k] == inf) continue;   // (also: an excised slot)
-        // first visit: link_k still holds the candidate's tot_cost (:309-311's parenthesis = tot_cost - cost[dst])
-        if (fresh) kk[k] = kk[k] - Dec(LoadCostEnc(&u.tok_cost[dst[k]]));
-        float lec = nx[k] + kk[k];
-        if (lec > lb) continue;
-        if (lec < 0.0f) lec = 0.0f;
-        __hip_atomic_fetch_min(x(src[k] - b), Enc(lec), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        SurvAddLink(u, sh, l0 + k, f);
+        for (int k = 0; k < kBU * kFinalPre; k++) nx[k] = dd[k] >= 0 ? LoadExtra(&u.tok_extra[dd[k]]) : inf;
+#pragma unroll
+        for (int k = 0; k < kBU * kFinalPre; k++) hit |= nx[k] != inf ? 1u << k : 0u;
+      } else {
+        uint32_t r[kBU * kFinalPre], w[kBU * kFinalPre];
+#pragma unroll
+        for (int k = 0; k < kBU * kFinalPre; k++) {
+          // (an excised slot, or one beyond the block's end: -1 - b1 is a huge unsigned number)
+          r[k] = min(static_cast<uint32_t>(dd[k] - b1), static_cast<uint32_t>(kFinalDense));
+          w[k] = mb_bits[r[k] >> 5];
+        }
+#pragma unroll
+        for (int k = 0; k < kBU * kFinalPre; k++) hit |= ((w[k] >> (r[k] & 31u)) & 1u) << k;
+      }
+      while (hit != 0u) {   // (a lane with a survivor: rare)
+        const int k = __ffs(hit) - 1;
+        hit &= hit - 1u;
+        int dst = dd[0];
+#pragma unroll
+        for (int j = 1; j < kBU * kFinalPre; j++) dst = k == j ? dd[j] : dst;
+        const int l = base + ((k >> 2) * NT + t) * kBU + (k & 3);
+        const uint32_t q = static_cast<uint32_t>(l - mb), rd = static_cast<uint32_t>(dst - b1);
+        int pos = kSweepList;
+        if (q < (1u << 18) && rd < (1u << 14)) pos = __hip_atomic_fetch_add(sl_n, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (pos < kSweepList) sl_e[pos] = (q << 14) | rd;
+        else survive(l, dst);   // (the list is full, or the pair does not fit a word: on the spot)
+      }
+      base += NT * kBU * kFinalPre;
+      if (base >= me) break;
+      // (a frame of more than NT * kBU * kFinalPre link slots: the remainder, a round trip per round)
+      d0 = LoadDst4(u, base + t * kBU, me); d1 = LoadDst4(u, base + (NT + t) * kBU, me);
+    }
+    // ---- requested here, to arrive under the barriers that follow: the epsilon links' three words, and the NEXT visit's
+    // destinations (not for a frame that will take the general route; link_dst is not written by a dense visit)
+    const bool eps_lane = ne > nb && ne - nb <= NT;   // the epsilon links one per lane (nearly every frame: a few hundred slots)
+    int edst = -1, esrc = b;
+    float ekk = 0.0f;
+    if (eps_lane && t < ne - nb) { edst = u.link_dst[nb + t]; esrc = u.link_src[nb + t]; ekk = u.link_k[nb + t]; }
+    have_pre = f > 0 && Uni(ve) - Uni(vb) <= kFinalDense;
+    p0 = none4; p1 = none4;
+    if (have_pre) { const int nmb = Uni(vmb), nme = Uni(vme); p0 = LoadDst4(u, nmb + t * kBU, nme); p1 = LoadDst4(u, nmb + (NT + t) * kBU, nme); }
+    LdsSync();   // the list: written by the sweep above, read below (and not written again before the next visit's first barrier)
+    {
+      const int nl = min(Uni(*sl_n), kSweepList);
+      for (int j = t; j < nl; j += NT) {
+        const uint32_t e = sl_e[j];
+        survive(mb + static_cast<int>(e >> 14), b1 + static_cast<int>(e & 0x3fffu));
       }
     }
+    XS(51);
     // ---- epsilon links (inside the frame): relax in place to the fixed point
-    if (ne > nb && ne - nb <= NT) {
-      // (nearly every frame: a few hundred slots) one link per lane, held in registers over the rounds; one barrier per
+    if (eps_lane) {
+      // one link per lane, held in registers over the rounds; one barrier per
       // round - the vote's - which also orders the round's minima before the next round's reads, and does not wait
       // for the survivor lists' stores
       LdsSync();
-      int dst = -1, src = b;
-      float kk = 0.0f;
-      if (t < ne - nb) { dst = u.link_dst[nb + t]; src = u.link_src[nb + t]; kk = u.link_k[nb + t]; }
+      XS(52);
+      const int dst = edst, src = esrc;
+      const float kk = ekk;
       for (;;) {
         bool changed = false;
         if (dst >= 0) {
@@ -4781,11 +4880,14 @@ __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb
     }
     // ---- the frame's survivors: listed, and handed to the next visit.  (Every reader of the map of frame f + 1 is
     // behind a barrier by now.)
+    XS(54);
     const int n_next = f > 0 ? Uni(ve) - Uni(vb) : 0;
     bool to_global = n_next > kFinalDense;
     for (int i = t; i < kMapSlots; i += NT) mk[i] = 0u;
+    if (t < kMapBitWords) mb_bits[t] = 0u;
     if (t == 0) { sh->map_n = 0; sh->flag = 0; }
     LdsSync();
+    XS(55);
     if (!to_global) {
       for (int i = t; i < n; i += NT) {
         const uint32_t xe = *x(i);
@@ -4801,6 +4903,7 @@ __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb
           sl = (sl + 1) & (kMapSlots - 1);
         }
         mv[sl] = Dec(xe);
+        __hip_atomic_fetch_or(&mb_bits[i >> 5], 1u << (i & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
       LdsSync();
       to_global = Uni(sh->flag) != 0;
@@ -4817,7 +4920,9 @@ __device__ void FinalBackward(const Utt &u_in, const Params &p, int last, int fb
     if (t == 0 && to_global) sh->sched[3] += 1;
     nx_global = to_global;
     b1 = b; e1 = e;
+    XS(56);
     KhSync();
+    XS(57);
   }
   if (prof) { sh->phase[40] += sh->sched[1]; sh->phase[41] += sh->sched[2]; sh->phase[42] += sh->sched[3]; sh->phase[43] += sh->surv_nt; sh->phase[44] += sh->surv_nl; }
 }

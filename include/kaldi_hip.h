@@ -1471,6 +1471,60 @@ int kh_tree_tile(void);
  * (one wave per event with a frame and block of 64 columns), frames of the longest event. */
 int kh_tree_last_timings(float *ms, int32_t *counts);
 
+/* ------------------------------------------------------------------ Gaussian selection (csrc/kh_gselect.hip)
+ * gmm-gselect and the gselect branch of gmm-global-acc-stats for a batch of stacked frames and ONE DiagGmm (gconsts [G],
+ * means_invvars / inv_vars [G x D], DEVICE; feats DEVICE, T x D, row pitch feat_stride).
+ *
+ * kh_gmm_gselect: DiagGmm::GaussianSelection(const MatrixBase&, ...) (gmm/diag-gmm.cc:801-871), its per-frame form (:765-799)
+ * and, with a preselection, GaussianSelectionPreselect (:875-916).  pre_offsets [T + 1] / pre_gauss (HOST, CSR; both NULL:
+ * no preselection).  DEVICE outputs: sel [T x n_out] int32, n_out = min(num_gselect, num_gauss), a frame's Gaussians best
+ * first, padded with -1; sel_count [T]; frame_like [T]; status [T].
+ *   Scores: without a preselection kh_diag_gmm_loglikes' values bit for bit (that call, on row chunks into a workspace); with
+ *   one the same k-ordered fmaf chains over the listed Gaussians, ll = (g + a1) + (-0.5f * a2).  This is the library's one
+ *   order for both branches of DiagGmm::LogLikelihoodsPreselect (:566-598): the reference takes BLAS on a contiguous range of
+ *   indices and VecVec per Gaussian otherwise.  (It decides "contiguous" from the first and last index alone, :575, so an
+ *   unsorted list with back + 1 - front == size is scored there as that RANGE; the library scores the Gaussians listed.)
+ *   Selection: the reference's nth_element, >= thresh, std::sort by std::greater<pair<float, int32>>, first n - that is, the
+ *   n largest under the total order (score descending, then index descending), scores compared as floats (+0 == -0: the index
+ *   decides); with a preselection position p carries preselect[p] as its index and n = min(num_gselect, list size) per frame.
+ *   frame_like: tot = LogAdd(tot, score_j) over the selected, best first, from -inf - the float LogAdd (base/kaldi-math.h:
+ *   198-215), Exp and Log1p being the float of the double function.
+ *   A frame with a NaN score (the reference's nth_element is undefined there): status 1, sel_count 0, its row of sel -1,
+ *   frame_like NaN; the call still returns KH_OK and the other frames have status 0.
+ * Before any launch, KH_EINVAL naming the offender: num_gauss outside 1 ... kh_gselect_max_gauss (4096), num_gselect outside
+ * 1 ... kh_gselect_max_n (128), D outside 1 ... kh_gselect_max_dim (96, kh_diag_gmm_loglikes'), feat_stride below D; of a
+ * preselection: offsets not from 0 or running backwards, an index outside [0, num_gauss), an empty list, a list longer than
+ * num_gauss (a Gaussian MAY be listed twice here, as in the reference).  T = 0 is valid. */
+int kh_gmm_gselect(const float *feats, int T, int D, int feat_stride, const float *gconsts, const float *means_invvars,
+                   const float *inv_vars, int num_gauss, int num_gselect, const int64_t *pre_offsets, const int32_t *pre_gauss,
+                   int32_t *sel, int32_t *sel_count, float *frame_like, int32_t *status);
+/* gmm-global-acc-stats.cc:117-131 up to the accumulation: per frame whose weight is not 0 (:119; frame_weight HOST [T], NULL:
+ * every weight 1), DiagGmm::LogLikelihoodsPreselect over the frame's list (the chains above), VectorBase::ApplySoftMax
+ * (matrix/kaldi-vector.cc:840-847) in LIST order, Scale(weight): float max; e = fl32(exp((double)(f - max))); the float sum of
+ * e in list order; (e * fl32(1.0 / sum)) * w; like = max + fl32(log((double)sum)) - kh_gmm_acc_component_posteriors'
+ * arithmetic.  The selection is HOST, CSR: sel_offsets [T + 1], sel_gauss.  DEVICE outputs: post, one dense zero-filled row
+ * of num_gauss floats per used frame, contiguous, in frame order - what kh_gmm_acc_stats takes for a one-pdf model
+ * (pdf_offsets = [0, num_gauss], one entry per used frame); frame_like [T], 0 for a frame that is not used.
+ * Before any launch, KH_EINVAL naming the frame: offsets not from 0 or running backwards; on a used frame an index outside
+ * [0, num_gauss), an empty list (the reference asserts gselect_size > 0), a Gaussian twice in the list.  The last is the one
+ * deliberate difference from the reference, which would add both posteriors: gmm-gselect never writes a duplicate, and a dense
+ * row holds one value per Gaussian. */
+int kh_gmm_preselect_posteriors(const float *feats, int T, int D, int feat_stride, const float *gconsts, const float *means_invvars,
+                                const float *inv_vars, int num_gauss, const int64_t *sel_offsets, const int32_t *sel_gauss,
+                                const float *frame_weight, float *post, float *frame_like);
+/* kh_gmm_gselect without a preselection scores at most this many bytes of T x num_gauss floats at a time (calling thread;
+ * 0 = the default, 256 MiB; at least one row).  No result depends on it. */
+int kh_gselect_set_workspace_limit(size_t bytes);
+int kh_gselect_max_gauss(void);
+int kh_gselect_max_n(void);
+int kh_gselect_max_dim(void);
+/* Lists (or num_gauss) up to this length take the kernels' small form, longer ones the large form (the tests' edge sizes). */
+int kh_gselect_small_lists(void);
+/* ms[5]: milliseconds of the calling thread's last kh_gmm_gselect - the whole call, its score kernels alone, its selection
+ * kernels alone (device events) - and of its last kh_gmm_preselect_posteriors - the whole call, its kernel alone.  counts[2]:
+ * row chunks of the gselect call; used frames of the posteriors call. */
+int kh_gselect_last_timings(float *ms, int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

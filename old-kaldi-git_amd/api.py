@@ -3494,6 +3494,157 @@ def add_gmm_stats(into, acc):
         raise KhError(str(e))
 
 
+# ---------------------------------------------------------------- Gaussian selection, global GMM statistics (csrc/kh_gselect.hip)
+# gmm-gselect and gmm-global-acc-stats for stacked frames and one DiagGmm: an AmDiagGmm of ONE pdf (diag_gmm makes it).
+def diag_gmm(weights, means_invvars, inv_vars, device="cuda"):
+    """A DiagGmm (kaldi_io.read_diag_gmm's arrays) on the device, gconsts computed as DiagGmm::Read does: an AmDiagGmm of one pdf."""
+    g, _ = gmm_compute_gconsts(weights, means_invvars, inv_vars)
+    return AmDiagGmm(g, means_invvars, inv_vars, np.asarray([0, len(g)], np.int32), device=device)
+
+
+def _one_gmm(gmm, feats, what):
+    if gmm.num_pdfs != 1:
+        raise KhError("%s: a single DiagGmm is needed, the model has %d pdfs" % (what, gmm.num_pdfs))
+    T, D, stride = _feat_args(feats)
+    if D != gmm.dim:
+        raise KhError("DiagGmm::ComponentLogLikelihood, dimension mismatch %d vs. %d" % (D, gmm.dim))
+    return T, D, stride
+
+
+def _csr_lists(lists, T, what):
+    """A list per frame -> (offsets int64 [T + 1], items int32)."""
+    if len(lists) != T:
+        raise KhError("%s: %d lists for %d frames" % (what, len(lists), T))
+    off = np.zeros(T + 1, np.int64)
+    if T:
+        off[1:] = np.cumsum([len(v) for v in lists])
+    items = np.concatenate([np.asarray(v, np.int32).reshape(-1) for v in lists]).astype(np.int32) if int(off[-1]) else np.zeros(1, np.int32)
+    return off, np.ascontiguousarray(items)
+
+
+def gmm_gselect(gmm, feats, n, preselect=None):
+    """DiagGmm::GaussianSelection for every stacked frame (kh_gmm_gselect), or GaussianSelectionPreselect when preselect (a
+    list of Gaussians per frame) is given.  gmm: an AmDiagGmm of one pdf; feats: 2-D float32 device tensor.  Returns
+    dict(lists: per frame an int32 array, best first; frame_like float32 [T]; status int32 [T], 1 for a frame with a NaN score,
+    which has no selection).  The order, the scores and frame_like are stated in include/kaldi_hip.h."""
+    T, D, stride = _one_gmm(gmm, feats, "gmm_gselect")
+    G, n = gmm.num_mix, int(n)
+    n_out = max(1, min(n, G))
+    dev = feats.device
+    sel = torch.empty((max(T, 1), n_out), dtype=torch.int32, device=dev)
+    cnt = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+    like = torch.empty(max(T, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+    po = pg = None
+    if preselect is not None:
+        off, items = _csr_lists(preselect, T, "gmm_gselect")
+        po, pg = off.ctypes.data_as(capi.c_int64_p), items.ctypes.data_as(capi.c_int32_p)
+    check(lib().kh_gmm_gselect(_p(feats), T, D, stride, _p(gmm.gconsts), _p(gmm.means_invvars), _p(gmm.inv_vars), G, n, po, pg,
+                               _p(sel), _p(cnt), _p(like), _p(status)))
+    sel, cnt = sel[:T].cpu().numpy(), cnt[:T].cpu().numpy()
+    return dict(lists=[sel[t, :cnt[t]].copy() for t in range(T)], frame_like=like[:T].cpu().numpy(), status=status[:T].cpu().numpy())
+
+
+def gmm_preselect_posteriors(gmm, feats, gselect, weights=None):
+    """The gselect branch of gmm-global-acc-stats.cc:117-131 up to the accumulation (kh_gmm_preselect_posteriors): per frame
+    whose weight is not 0, LogLikelihoodsPreselect, ApplySoftMax in list order, Scale(weight).  gselect: a list of Gaussians per
+    frame; weights: per frame, or None.  Returns (post, frame_like, used): post a float32 device tensor [used frames x
+    num_gauss], dense and zero outside the lists; frame_like float32 host [T], 0 for a skipped frame; used: the frames that
+    were not skipped, host int32.  A list that is empty or names a Gaussian twice on a used frame raises, naming the frame."""
+    T, D, stride = _one_gmm(gmm, feats, "gmm_preselect_posteriors")
+    off, items = _csr_lists(gselect, T, "gmm_preselect_posteriors")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if len(w) != T:
+            raise KhError("gmm_preselect_posteriors: %d weights for %d frames" % (len(w), T))
+    used = np.arange(T, dtype=np.int32) if w is None else np.nonzero(w != 0)[0].astype(np.int32)
+    G = gmm.num_mix
+    post = torch.empty((max(len(used), 1), G), dtype=torch.float32, device=feats.device)
+    like = torch.empty(max(T, 1), dtype=torch.float32, device=feats.device)
+    check(lib().kh_gmm_preselect_posteriors(_p(feats), T, D, stride, _p(gmm.gconsts), _p(gmm.means_invvars), _p(gmm.inv_vars), G,
+                                            off.ctypes.data_as(capi.c_int64_p), items.ctypes.data_as(capi.c_int32_p),
+                                            w.ctypes.data_as(capi.c_float_p) if w is not None else None, _p(post), _p(like)))
+    return post[:len(used)], like[:T].cpu().numpy(), used
+
+
+def _used_entries(used, T, G):
+    """The entry list kh_gmm_acc_stats takes for a one-pdf model: one entry per used frame."""
+    feo = np.zeros(T + 1, np.int64)
+    feo[np.asarray(used, np.int64) + 1] = 1
+    feo = np.cumsum(feo)
+    n = len(used)
+    return dict(feo=feo, pdf=np.zeros(n, np.int32), weight=np.ones(n, np.float32), goff=np.arange(n + 1, dtype=np.int64) * G)
+
+
+def accumulate_global_gmm_stats(gmm, feats, gselect=None, weights=None, flags="mvw", into=None):
+    """The frame loop of gmm-global-acc-stats.cc:117-139 for the stacked frames of ONE utterance or batch.  With gselect:
+    gmm_preselect_posteriors, then gmm_acc_stats unchanged on the dense posteriors (a zero posterior adds +-0 to a double sum,
+    so the sums are those over the selected items).  Without: AccumulateFromDiag - gmm_acc_component_posteriors on the one-pdf
+    model with the frame weights as entry weights, then gmm_acc_stats.  A frame of weight 0 is skipped.  Returns dict(occ,
+    mean_acc, var_acc, dim, flags, file_like, file_weight): file_like is the reference's FLOAT running sum file_like += weight
+    * like in frame order, file_weight the float sum of the weights, both made on the host.  into: a dict this function
+    returned, whose occ / mean_acc / var_acc are added to in double (file_like / file_weight are this call's)."""
+    T, D, stride = _one_gmm(gmm, feats, "accumulate_global_gmm_stats")
+    G = gmm.num_mix
+    bits = gmm_flags(flags)
+    w = np.ones(T, np.float32) if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if len(w) != T:
+        raise KhError("accumulate_global_gmm_stats: %d weights for %d frames" % (len(w), T))
+    if gselect is not None:
+        post, like, used = gmm_preselect_posteriors(gmm, feats, gselect, None if weights is None else w)
+        ent = _used_entries(used, T, G)
+        post = post.reshape(-1)
+    else:
+        used = np.nonzero(w != 0)[0].astype(np.int32)
+        ent = _used_entries(used, T, G)
+        ent["weight"] = w[used]
+        like = np.zeros(T, np.float32)
+        if len(used):
+            post, el = gmm_acc_component_posteriors(gmm, feats, ent)
+            like[used] = el.cpu().numpy()
+        else:
+            post = torch.zeros(0, dtype=torch.float32, device=feats.device)
+    acc = gmm_acc_stats(gmm, feats, ent, post, bits) if T else dict(
+        occ=np.zeros(G), mean_acc=np.zeros((G, D)) if bits & kGmmMeans else None, var_acc=np.zeros((G, D)) if bits & kGmmVariances else None)
+    file_like, file_weight = np.float32(0.0), np.float32(0.0)
+    for t in used:
+        file_weight = np.float32(file_weight + w[t])
+        file_like = np.float32(file_like + np.float32(w[t] * like[t]))
+    acc.update(dim=D, flags=bits, file_like=file_like, file_weight=file_weight, frame_like=like)
+    if into is not None:
+        from . import kaldi_io
+        try:
+            kaldi_io.add_global_gmm_accs(into, acc)
+        except ValueError as e:
+            raise KhError(str(e))
+        into.update(file_like=file_like, file_weight=file_weight, frame_like=like)
+        return into
+    return acc
+
+
+def gselect_max_gauss():
+    return int(lib().kh_gselect_max_gauss())
+
+
+def gselect_max_n():
+    return int(lib().kh_gselect_max_n())
+
+
+def gselect_set_workspace_limit(nbytes):
+    """gmm_gselect without a preselection scores at most nbytes of frames x Gaussians floats at a time (calling thread;
+    0 = 256 MiB).  No result depends on it."""
+    check(lib().kh_gselect_set_workspace_limit(int(nbytes)))
+
+
+def gselect_last_timings():
+    """The calling thread's last gmm_gselect (call, score kernels, selection kernels) and gmm_preselect_posteriors (call,
+    kernel) in milliseconds; row chunks of the former, used frames of the latter."""
+    return _timings(lib().kh_gselect_last_timings,
+                    ("gselect_call_ms", "score_kernels_ms", "select_kernels_ms", "posteriors_call_ms", "posteriors_kernel_ms"),
+                    ("row_chunks", "used_frames"))
+
+
 # ---------------------------------------------------------------- MLLT statistics (csrc/kh_mllt.hip)
 # gmm-acc-mllt for stacked frames, over the same entry lists.  An accumulator is dict(beta, G [D, D (D + 1) / 2] float64, dim):
 # row j of G is the packed lower triangle of MlltAccs' G_[j].

@@ -282,6 +282,15 @@ SIGNATURES = {
     "kh_tree_max_dim": (C.c_int, []),
     "kh_tree_tile": (C.c_int, []),
     "kh_tree_last_timings": (C.c_int, [c_float_p, c_int32_p]),
+    "kh_gmm_gselect": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, c_int64_p, c_int32_p, vp, vp, vp, vp]),
+    "kh_gmm_preselect_posteriors": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, c_int64_p, c_int32_p, c_float_p,
+                                              vp, vp]),
+    "kh_gselect_set_workspace_limit": (C.c_int, [C.c_size_t]),
+    "kh_gselect_max_gauss": (C.c_int, []),
+    "kh_gselect_max_n": (C.c_int, []),
+    "kh_gselect_max_dim": (C.c_int, []),
+    "kh_gselect_small_lists": (C.c_int, []),
+    "kh_gselect_last_timings": (C.c_int, [c_float_p, c_int32_p]),
     "kh_lattice_forward_backward_mpe": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, c_int32_p, C.c_int, C.c_int, c_float_p, c_double_p, c_int32_p]),
     "kh_rescore_lattice": (C.c_int, [C.c_int, c_int32_p, c_int64_p, c_int32_p, c_int32_p, c_float_p, vp, C.c_int, c_int32_p, vp]),
     "kh_merge_pair_vector_summing": (C.c_int, [i64, c_int32_p, c_int32_p, c_float_p, i32, c_int32_p, c_int32_p, c_float_p, c_int64_p]),

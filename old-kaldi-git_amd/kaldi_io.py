@@ -374,6 +374,32 @@ def _read_object(s, binary, kind):
                 break
             line += b
         return np.asarray([int(w) for w in line.split()], np.int32)
+    if kind == "int32_vector_vector":
+        # BasicVectorVectorHolder<int32>::Read (kaldi-holder-inl.h:347-408).  binary: the size, per inner vector its size and
+        # its elements, all as basic types; text: "1 2 3 ; 4 5 ; ; \n", the semicolon a terminator
+        if binary:
+            return [np.asarray([read_int32(s) for _ in range(read_int32(s))], np.int32) for _ in range(read_int32(s))]
+        out, v = [], []
+        while True:
+            if s.eof():
+                raise ValueError("Unexpected EOF")
+            b = s.peek()
+            if b == b"\n":
+                if v:
+                    raise ValueError("No semicolon before newline (wrong format)")
+                s.get()
+                return out
+            if b.isspace():
+                s.get()
+            elif b == b";":
+                out.append(np.asarray(v, np.int32))
+                v = []
+                s.get()
+            else:
+                word = bytearray()          # operator >> (int32 &): it stops at the semicolon too
+                while not s.eof() and not s.peek().isspace() and s.peek() != b";":
+                    word += s.get()
+                v.append(int(word))
     if kind == "compact_lattice":
         return read_compact_lattice(s, binary)
     if kind == "compact_lattice_converted":
@@ -404,6 +430,15 @@ def _write_object(f, binary, kind, obj):
                 write_int32(f, True, x)
         else:
             f.write(b"".join(b"%d " % int(x) for x in v) + b"\n")
+    elif kind == "int32_vector_vector":  # BasicVectorVectorHolder<int32>::Write (kaldi-holder-inl.h:302-342)
+        if binary:
+            write_int32(f, True, len(obj))
+            for v in obj:
+                write_int32(f, True, len(v))
+                for x in v:
+                    write_int32(f, True, int(x))
+        else:
+            f.write(b"".join(b"".join(b"%d " % int(x) for x in v) + b"; " for v in obj) + b"\n")
     elif kind == "lattice":
         write_lattice(f, obj, binary)
     elif kind == "compact_lattice":
@@ -1701,6 +1736,90 @@ def _flags_string(bits):
     return "".join(c for c, b in (("m", 1), ("v", 2), ("w", 4), ("t", 8)) if bits & b)
 
 
+def _write_accum_diag_gmm(f, acc, g0, g1, binary):
+    """AccumDiagGmm::Write (gmm/mle-diag-gmm.cc:77-103) for the Gaussians g0 .. g1 - 1 of acc."""
+    empty = np.zeros((0, 0), np.float32)
+    write_token(f, binary, "<GMMACCS>")
+    write_token(f, binary, "<VECSIZE>")
+    write_int32(f, binary, int(acc["dim"]))
+    write_token(f, binary, "<NUMCOMPONENTS>")
+    write_int32(f, binary, g1 - g0)
+    write_token(f, binary, "<FLAGS>")
+    f.write(b"\xfe" + struct.pack("<H", int(acc["flags"])) if binary else b"%d " % int(acc["flags"]))
+    write_token(f, binary, "<OCCUPANCY>")
+    write_vector(f, np.asarray(acc["occ"][g0:g1], np.float64).astype(np.float32), binary)
+    write_token(f, binary, "<MEANACCS>")
+    write_matrix(f, empty if acc["mean_acc"] is None else np.asarray(acc["mean_acc"][g0:g1], np.float64).astype(np.float32), binary)
+    write_token(f, binary, "<DIAGVARACCS>")
+    write_matrix(f, empty if acc["var_acc"] is None else np.asarray(acc["var_acc"][g0:g1], np.float64).astype(np.float32), binary)
+    write_token(f, binary, "</GMMACCS>")
+
+
+def _read_accum_diag_gmm(s, binary):
+    """AccumDiagGmm::Read (gmm/mle-diag-gmm.cc:33-75) without the adding: (dim, num_components, flags, occ, mean, var), the
+    floats of the file widened to double; an accumulator the flags exclude is None."""
+    expect_token(s, binary, "<GMMACCS>")
+    expect_token(s, binary, "<VECSIZE>")
+    dim = read_int32(s, binary)
+    expect_token(s, binary, "<NUMCOMPONENTS>")
+    n = read_int32(s, binary)
+    expect_token(s, binary, "<FLAGS>")
+    if binary:
+        if s.get() != b"\xfe":
+            raise ValueError("ReadBasicType: did not get expected integer type (GmmFlagsType, -2)")
+        flags = struct.unpack("<H", s.get(2))[0]
+    else:
+        flags = int(_text_word(s))
+    o = np.zeros(n, np.float64)
+    m = np.zeros((n, dim), np.float64) if flags & 1 else None
+    v = np.zeros((n, dim), np.float64) if flags & 2 else None
+    tok = read_token(s, binary)
+    while tok != "</GMMACCS>":
+        if tok == "<OCCUPANCY>":
+            o = read_vector(s, binary).astype(np.float64)
+        elif tok == "<MEANACCS>":
+            x = read_matrix(s, binary).astype(np.float64)
+            m = x if flags & 1 else None
+        elif tok == "<DIAGVARACCS>":
+            x = read_matrix(s, binary).astype(np.float64)
+            v = x if flags & 2 else None
+        else:
+            raise ValueError("Unexpected token '%s' in model file " % tok)
+        tok = read_token(s, binary)
+    if len(o) != n or (m is not None and m.shape != (n, dim)) or (v is not None and v.shape != (n, dim)):
+        raise ValueError("AccumDiagGmm::Read: accumulators do not have the sizes of the header (%d, %d)" % (n, dim))
+    return dim, n, flags, o, m, v
+
+
+# The stand-alone AccumDiagGmm file between gmm-global-acc-stats, gmm-global-sum-accs and gmm-global-est: one <GMMACCS> block,
+# no transition accumulators, no <NUMPDFS>, no totals.  A global accumulator is dict(occ [G], mean_acc [G, D] | None,
+# var_acc [G, D] | None (float64), dim, flags).
+def write_global_gmm_accs(f, acc, binary=True):
+    """AccumDiagGmm::Write (gmm/mle-diag-gmm.cc:77-103): the accumulators are converted to float before writing."""
+    _write_accum_diag_gmm(f, acc, 0, len(acc["occ"]), binary)
+
+
+def add_global_gmm_accs(into, acc):
+    """into += acc in double, with the check and message of AccumDiagGmm::Read(..., add = true) (mle-diag-gmm.cc:46-54)."""
+    if len(into["occ"]) != len(acc["occ"]) or int(into["dim"]) != int(acc["dim"]) or int(into["flags"]) != int(acc["flags"]):
+        raise ValueError("MlEstimatediagGmm::Read, dimension or flags mismatch, %d, %d, %s vs. %d, %d, %d (mixing accs from different models?"
+                         % (len(into["occ"]), into["dim"], _flags_string(int(into["flags"])), len(acc["occ"]), acc["dim"], acc["flags"]))
+    for k in ("occ", "mean_acc", "var_acc"):
+        if into[k] is not None:
+            into[k] += acc[k]
+    return into
+
+
+def read_global_gmm_accs(s, binary=True, add_into=None):
+    """AccumDiagGmm::Read (gmm/mle-diag-gmm.cc:33-75).  add_into: an accumulator the values read are added to, as
+    Read(..., add = true) does - an empty one (no Gaussians, dimension 0, flags 0: :47) takes the file's sizes."""
+    dim, n, flags, o, m, v = _read_accum_diag_gmm(_as_stream(s), binary)
+    acc = dict(occ=o, mean_acc=m, var_acc=v, dim=dim, flags=flags)
+    if add_into is None or (len(add_into["occ"]) == 0 and int(add_into["dim"]) == 0 and int(add_into["flags"]) == 0):
+        return acc
+    return add_global_gmm_accs(add_into, acc)
+
+
 def write_gmm_accs(f, acc, binary=True, tail=True):
     """The body of an .acc file: Vector<double>::Write of the transition accumulators (when acc carries them), then
     AccumAmDiagGmm::Write (gmm/mle-am-diag-gmm.cc:153-166) over AccumDiagGmm::Write (gmm/mle-diag-gmm.cc:77-103): the
@@ -1711,23 +1830,8 @@ def write_gmm_accs(f, acc, binary=True, tail=True):
         write_vector(f, np.asarray(acc["transition_accs"], np.float64), binary)
     write_token(f, binary, "<NUMPDFS>")
     write_int32(f, binary, len(off) - 1)
-    empty = np.zeros((0, 0), np.float32)
     for j in range(len(off) - 1):
-        g0, g1 = int(off[j]), int(off[j + 1])
-        write_token(f, binary, "<GMMACCS>")
-        write_token(f, binary, "<VECSIZE>")
-        write_int32(f, binary, int(acc["dim"]))
-        write_token(f, binary, "<NUMCOMPONENTS>")
-        write_int32(f, binary, g1 - g0)
-        write_token(f, binary, "<FLAGS>")
-        f.write(b"\xfe" + struct.pack("<H", int(acc["flags"])) if binary else b"%d " % int(acc["flags"]))
-        write_token(f, binary, "<OCCUPANCY>")
-        write_vector(f, np.asarray(acc["occ"][g0:g1], np.float64).astype(np.float32), binary)
-        write_token(f, binary, "<MEANACCS>")
-        write_matrix(f, empty if acc["mean_acc"] is None else np.asarray(acc["mean_acc"][g0:g1], np.float64).astype(np.float32), binary)
-        write_token(f, binary, "<DIAGVARACCS>")
-        write_matrix(f, empty if acc["var_acc"] is None else np.asarray(acc["var_acc"][g0:g1], np.float64).astype(np.float32), binary)
-        write_token(f, binary, "</GMMACCS>")
+        _write_accum_diag_gmm(f, acc, int(off[j]), int(off[j + 1]), binary)
     if tail:
         write_token(f, binary, "<total_like>")
         f.write(b"\x08" + struct.pack("<d", float(acc["total_like"])) if binary else (_fmt(acc["total_like"]) + " ").encode())
@@ -1784,36 +1888,7 @@ def read_gmm_accs(s, binary=True, add_into=None, transitions=True):
         raise ValueError("Adding accumulators but num-pdfs do not match: %d vs. %d" % (len(add_into["pdf_offsets"]) - 1, num_pdfs))
     occ, mean, var, off, dims, flagset = [], [], [], [0], set(), set()
     for _ in range(num_pdfs):
-        expect_token(s, binary, "<GMMACCS>")
-        expect_token(s, binary, "<VECSIZE>")
-        dim = read_int32(s, binary)
-        expect_token(s, binary, "<NUMCOMPONENTS>")
-        n = read_int32(s, binary)
-        expect_token(s, binary, "<FLAGS>")
-        if binary:
-            if s.get() != b"\xfe":
-                raise ValueError("ReadBasicType: did not get expected integer type (GmmFlagsType, -2)")
-            flags = struct.unpack("<H", s.get(2))[0]
-        else:
-            flags = int(_text_word(s))
-        o = np.zeros(n, np.float64)
-        m = np.zeros((n, dim), np.float64) if flags & 1 else None
-        v = np.zeros((n, dim), np.float64) if flags & 2 else None
-        tok = read_token(s, binary)
-        while tok != "</GMMACCS>":
-            if tok == "<OCCUPANCY>":
-                o = read_vector(s, binary).astype(np.float64)
-            elif tok == "<MEANACCS>":
-                x = read_matrix(s, binary).astype(np.float64)
-                m = x if flags & 1 else None
-            elif tok == "<DIAGVARACCS>":
-                x = read_matrix(s, binary).astype(np.float64)
-                v = x if flags & 2 else None
-            else:
-                raise ValueError("Unexpected token '%s' in model file " % tok)
-            tok = read_token(s, binary)
-        if len(o) != n or (m is not None and m.shape != (n, dim)) or (v is not None and v.shape != (n, dim)):
-            raise ValueError("AccumDiagGmm::Read: accumulators do not have the sizes of the header (%d, %d)" % (n, dim))
+        dim, n, flags, o, m, v = _read_accum_diag_gmm(s, binary)
         occ.append(o); mean.append(m); var.append(v)
         off.append(off[-1] + n)
         dims.add(dim)
